@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BA iterations on synthetic N-camera x M-observation scenes, 1..8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config I] [--solver trf|lm]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config I] [--solver trf|lm] [--full] [--dump-outputs DIR]
 
 A *step* is one bundle-adjustment iteration = one trust-region trial of ``Scene.BA``:
 residual + Jacobian at x, one linear solve for the step, residual at the trial point
@@ -18,10 +18,17 @@ detections of one time slice and that slice of the spline blocks, and the ranks 
 blocks + halo, separator system, Schur contributions, step) over RCCL; ``--shard obs`` (always used by ``--solver trf``)
 cuts every camera's detections into N pieces instead, with one all-reduce per J^T u / dot product / normal-equation set.
 
-The JSON line also carries the roofline of the dominant kernel (residual+Jacobian), measured with
-HIP events on the kernel's own stream, and a CPU baseline (the oracle's restatement of the scipy path,
-one core) on a bounded sample, on rank 0 at N=1 only.  ``long_solve`` (LM): the same number of trials inside ONE call, measured after
-the timed region -- what an iteration costs inside a long Scene.BA (no residual at the start of each call, no Python between trials).
+A plain run sets up, warms up, times the K steps and prints the JSON line (``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step`` and the workload).  Everything else is measured only with ``--full``:
+the roofline of the dominant kernel (residual+Jacobian), measured with HIP events on the kernel's own stream, the
+per-kernel times, and a CPU baseline (the oracle's restatement of the scipy path, one core) on a bounded sample, on
+rank 0 at N=1 only.  ``long_solve`` (LM): the same number of trials inside ONE call, measured after the timed region --
+what an iteration costs inside a long Scene.BA (no residual at the start of each call, no Python between trials).
+``--full`` also times the reference-faithful solver on the same workload (N=1) and the strong-scaling sub-record (N>1).
+
+``--dump-outputs DIR``: after the timed steps, rank 0 writes what the last timed step returned to its caller as
+``DIR/<name>.npy`` (float64): the parameter vector ``x`` and the scalars ``cost``, ``initial_cost``, ``optimality``,
+``nfev``, ``njev``, ``status``.  The scene is seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -44,6 +51,29 @@ def algorithmic_bytes(prob):
     per_obs = (24 if prob.opt_calib else 32) + 16 + 2 * NS * 8 + 4
     once = (prob.n_params + prob.knots.size + 10 * prob.C) * 8
     return per_obs, once
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res):
+    """What the last timed step returned to its caller (``handle.solve(..., return_fun=False)``), one float64 .npy per
+    array; an array above the size limit is replaced by a fixed, seeded sample of its entries (``<name>_sample_idx.npy``
+    beside it)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'x': np.asarray(res.x, dtype=np.float64)}
+    for name in ('cost', 'initial_cost', 'optimality', 'nfev', 'njev', 'status'):
+        arrays[name] = np.array([getattr(res, name)], dtype=np.float64)
+    budget = DUMP_LIMIT_BYTES - sum(a.nbytes for k, a in arrays.items() if k != 'x')
+    x = arrays['x']
+    if x.nbytes > budget:
+        keep = budget // 16                              # the sampled values and their indices, 8 bytes each
+        idx = np.sort(np.random.default_rng(0).choice(x.size, size=keep, replace=False))
+        arrays['x'] = x[idx]
+        arrays['x_sample_idx'] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def cpu_baseline(config_index, full_scene=None, full_ba=False):
@@ -104,6 +134,10 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--full', action='store_true', help='also measure everything beside the headline: long_solve, roofline and per-kernel times, '
+                                                        'the reference-faithful solver, the CPU baseline (N=1), the configs[3] strong-scaling record (N>1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (x and the result scalars) as DIR/<name>.npy, float64')
     ap.add_argument('--no-long-solve', action='store_true', help='skip the one-call leg (long_solve in the JSON line)')
     ap.add_argument('--config', type=int, default=2, help='index into BASELINE.json configs (2 = 32 cams x 500k obs)')
     ap.add_argument('--solver', choices=['trf', 'lm'], default=os.environ.get('MVUS_BENCH_SOLVER', 'lm'))
@@ -119,6 +153,8 @@ def main():
                     help='N>1: rccl = ncclAllReduce called by the library on its own communicator; auto (default on a multi-GPU node) = rccl, or the callback if the library cannot open RCCL; '
                          'torch = the callback through torch.distributed (the only route of the one-device gloo flow test)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     import numpy as np
     import torch
@@ -199,11 +235,14 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r)
+
     # The same number of trials inside ONE call (what an iteration costs in a Scene.BA of many evaluations: no residual at the start of
     # every call -- the accepted trial's residual is the next iteration's -- and no return to Python between trials).  Reported beside
     # the headline, never as it; outside the timed region.
     long_solve = None
-    if args.solver == 'lm' and not args.no_long_solve:
+    if args.full and args.solver == 'lm' and not args.no_long_solve:
         barrier()
         tl = time.perf_counter()
         rl = handle.solve(x, solver=solver, jac_mode=jac_mode, max_nfev=args.steps + 1, return_fun=False, ties='canonical')
@@ -218,24 +257,41 @@ def main():
                               'linearisation (trials > linearisations - 1 then)'}
 
     gc.enable()
-    # roofline of the dominant kernel: residual + Jacobian, HIP events on the kernel's own stream
-    handle.set_x(x)
-    t_rj = handle.time_kernel(ba.KERNEL_RESIDUAL_JACOBIAN, 100)          # outputs rotate over >= 1 GiB: every launch goes to HBM
-    t_rj_one = handle.time_kernel(ba.KERNEL_RESIDUAL_JACOBIAN_ONE_BUFFER, 20)   # same kernel into one (Infinity-Cache sized) set
-    t_r = handle.time_kernel(ba.KERNEL_RESIDUAL, 50)
-    t_jv = handle.time_kernel(ba.KERNEL_JV, 50)
-    t_jtu = handle.time_kernel(ba.KERNEL_JTU, 50)
-    t_asm = handle.time_kernel(ba.KERNEL_ASSEMBLY, 20)
-    t_fused = handle.time_kernel(ba.KERNEL_FUSED_ASSEMBLY, 20)
-    per_obs, once = algorithmic_bytes(handle.prob)
-    bytes_launch = handle.prob.M * per_obs + once
-    achieved = bytes_launch / (t_rj * 1e-3) / 1e9
+    roofline = kernels_ms = None
+    if args.full:
+        # roofline of the dominant kernel: residual + Jacobian, HIP events on the kernel's own stream
+        handle.set_x(x)
+        t_rj = handle.time_kernel(ba.KERNEL_RESIDUAL_JACOBIAN, 100)          # outputs rotate over >= 1 GiB: every launch goes to HBM
+        t_rj_one = handle.time_kernel(ba.KERNEL_RESIDUAL_JACOBIAN_ONE_BUFFER, 20)   # same kernel into one (Infinity-Cache sized) set
+        t_r = handle.time_kernel(ba.KERNEL_RESIDUAL, 50)
+        t_jv = handle.time_kernel(ba.KERNEL_JV, 50)
+        t_jtu = handle.time_kernel(ba.KERNEL_JTU, 50)
+        t_asm = handle.time_kernel(ba.KERNEL_ASSEMBLY, 20)
+        t_fused = handle.time_kernel(ba.KERNEL_FUSED_ASSEMBLY, 20)
+        per_obs, once = algorithmic_bytes(handle.prob)
+        bytes_launch = handle.prob.M * per_obs + once
+        achieved = bytes_launch / (t_rj * 1e-3) / 1e9
+        traffic = None
+        tpath = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
+        if os.path.exists(tpath):
+            key = 'config%d_calib%d' % (args.config, int(prob.opt_calib))
+            traffic = json.load(open(tpath)).get(key, {}).get('bytes_per_launch')
+        roofline = {'bound': 'hbm', 'kernel': 'k_observations<calib=%s,jac=true>' % ('true' if prob.opt_calib else 'false'),
+                    'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                    'traffic': traffic, 'traffic_source': 'profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, gfx950 corrections applied)' if traffic else None,
+                    'bytes_per_launch': bytes_launch, 'avg_launch_ms': t_rj,
+                    'bytes_per_obs': per_obs, 'obs_per_launch': handle.prob.M,
+                    'timing': 'HIP events over 100 launches whose outputs rotate over >= 3 buffer sets (>= 1 GiB, 4x the Infinity Cache)',
+                    'one_buffer': {'avg_launch_ms': t_rj_one, 'achieved': bytes_launch / (t_rj_one * 1e-3) / 1e9,
+                                   'frac': bytes_launch / (t_rj_one * 1e-3) / 1e9 / HBM_PEAK_GBS}}
+        kernels_ms = {'residual': t_r, 'residual_jacobian': t_rj, 'jv': t_jv, 'jtu': t_jtu, 'normal_eq_assembly_from_J': t_asm,
+                      'fused_jacobian_normal_eq_assembly': t_fused}
 
     # the reference-faithful solver (scipy TRF + LSMR restated) on the same workload, a few steps, for the record: with the
     # Jacobian `Scene.BA` uses BY DEFAULT (scipy's grouped 2-point finite differences, MVUS_JAC_FD: what a user of an unmodified
     # config.json gets) and with the analytic Jacobian masked to the reference's pattern (MVUS_JAC_PATTERN)
     parity = None
-    if world == 1 and not args.no_parity_solver and args.solver == 'lm':      # (an N=1 report, like the CPU baseline)
+    if args.full and world == 1 and not args.no_parity_solver and args.solver == 'lm':      # (an N=1 report, like the CPU baseline)
         def timed(jm, prepare, nsteps=3):
             xs = x0.copy()
             t_prep = time.perf_counter()
@@ -273,16 +329,10 @@ def main():
         parity['default_fd'] = fd
         parity['default_fd_one_pass'] = fd1
 
-    traffic = None
-    tpath = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
-    if os.path.exists(tpath):
-        key = 'config%d_calib%d' % (args.config, int(prob.opt_calib))
-        traffic = json.load(open(tpath)).get(key, {}).get('bytes_per_launch')
-
     # N > 1 on a weak-scaling default: the node's strong-scaling figure on BASELINE configs[3] (64 cams x 2M obs cut over the ranks) as a
     # sub-record of the same line, so that a scaling run lands on a configuration BASELINE.json lists whichever default it was started with
     strong3 = None
-    if world > 1 and not strong and args.solver == 'lm' and not args.no_strong_config3:
+    if args.full and world > 1 and not strong and args.solver == 'lm' and not args.no_strong_config3:
         kw3 = dict(synth.BASELINE_CONFIGS[3])
         scene3 = synth.make_scene(**kw3)
         prob3, x03 = mp.problem_from_scene(scene3)
@@ -326,21 +376,11 @@ def main():
                        'solver': args.solver, 'parallelism': '%s-shard x%d' % (shard_mode, world),
                        'collective': getattr(handle, 'collective_used', None),      # 'rccl' = ncclAllReduce called by the library, 'torch' = callback
                        'cost_first': cost0, 'cost_last': r.cost},
-            'roofline': {'bound': 'hbm', 'kernel': 'k_observations<calib=%s,jac=true>' % ('true' if prob.opt_calib else 'false'),
-                         'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                         'traffic': traffic, 'traffic_source': 'profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, gfx950 corrections applied)' if traffic else None,
-                         'bytes_per_launch': bytes_launch, 'avg_launch_ms': t_rj,
-                         'bytes_per_obs': per_obs, 'obs_per_launch': handle.prob.M,
-                         'timing': 'HIP events over 100 launches whose outputs rotate over >= 3 buffer sets (>= 1 GiB, 4x the Infinity Cache)',
-                         'one_buffer': {'avg_launch_ms': t_rj_one, 'achieved': bytes_launch / (t_rj_one * 1e-3) / 1e9,
-                                        'frac': bytes_launch / (t_rj_one * 1e-3) / 1e9 / HBM_PEAK_GBS}},
-            'parity_solver': parity,
-            'strong_config3': strong3,
-            'long_solve': long_solve,
-            'kernels_ms': {'residual': t_r, 'residual_jacobian': t_rj, 'jv': t_jv, 'jtu': t_jtu, 'normal_eq_assembly_from_J': t_asm,
-                           'fused_jacobian_normal_eq_assembly': t_fused},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.update({'roofline': roofline, 'parity_solver': parity, 'strong_config3': strong3, 'long_solve': long_solve,
+                        'kernels_ms': kernels_ms})
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the SAME-size CPU figure by default: the oracle's 10-evaluation BA on the full workload (one core, ~50 s at configs[2]), beside the
             # bounded 1/32-scale sample; above 600k observations (configs[3]: minutes) only when asked for
             want_full = not args.no_cpu_full and (args.cpu_full or prob.M <= 600_000)

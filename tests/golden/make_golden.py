@@ -239,9 +239,9 @@ def run_case(common, name, sc, max_iters=(10,), seed=123, max_iters2=(10,)):
                 print('  %s second BA max_iter=%d: cost=%.9g nfev=%d njev=%d status=%d rmse=%.6f'
                       % (name, mi2, res2.cost, res2.nfev, res2.njev, res2.status, rmse2))
 
-    path = os.path.join(HERE, name + '.npz')
-    np.savez_compressed(path, **out)
-    print('wrote %s (%.1f KiB)' % (path, os.path.getsize(path) / 1024))
+    import golden_util
+    for path in golden_util.save_case(os.path.join(HERE, name + '.npz'), out):
+        print('wrote %s (%.1f KiB)' % (path, os.path.getsize(path) / 1024))
 
 
 def main():

@@ -14,9 +14,44 @@ CONFIG1_SHAPE = 'config1_shape_7cam'
 CONVERGED_CASES = CASES + [CALIB_WP, CONFIG1_SHAPE]
 
 
+PART_LIMIT_BYTES = 960 * 1024     # a case larger than this is stored as <case>.npz + <case>.part1.npz, .part2.npz, ...
+
+
+def save_case(path, arrays, limit=PART_LIMIT_BYTES):
+    """np.savez_compressed of one case, split over <case>.npz, <case>.part1.npz, ... (keys in order, disjoint) so that no
+    file exceeds ``limit`` bytes; load_case merges them back.  Returns the paths written."""
+    import io
+    import zlib
+    parts, size = [[]], 0
+    for k, a in arrays.items():
+        buf = io.BytesIO()
+        np.save(buf, np.asanyarray(a), allow_pickle=False)
+        n = len(zlib.compress(buf.getvalue(), 6)) + 256
+        if parts[-1] and size + n > limit:
+            parts.append([])
+            size = 0
+        parts[-1].append(k)
+        size += n
+    base = path[:-len('.npz')]
+    paths = [path] + ['%s.part%d.npz' % (base, i) for i in range(1, len(parts))]
+    for p, keys in zip(paths, parts):
+        np.savez_compressed(p, **{k: arrays[k] for k in keys})
+    return paths
+
+
+def load_case_arrays(name):
+    """The raw arrays of one case: <case>.npz and its .part<i>.npz files (if any) merged."""
+    g = dict(np.load(os.path.join(GOLDEN_DIR, name + '.npz'), allow_pickle=False))
+    i = 1
+    while os.path.exists(os.path.join(GOLDEN_DIR, '%s.part%d.npz' % (name, i))):
+        g.update(dict(np.load(os.path.join(GOLDEN_DIR, '%s.part%d.npz' % (name, i)), allow_pickle=False)))
+        i += 1
+    return g
+
+
 def load_case(name):
     """Return (scene, g): a scene object with the reference's attribute names and the raw npz dict."""
-    g = dict(np.load(os.path.join(GOLDEN_DIR, name + '.npz'), allow_pickle=False))
+    g = load_case_arrays(name)
     C = int(g['num_cam'])
     off = g['det_offsets']
     cams = [dict(K=g['cam_K'][i], d=g['cam_d'][i], R=g['cam_R'][i], t=g['cam_t'][i],

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/quick; mkdir -p $O
 T=${@:-tests/test_gpu_schur.py tests/test_gpu_dist.py}
 python -m pytest $T -x -q -m gpu > $O/tests.log 2>&1; grep -E "passed|failed|error" $O/tests.log | tail -3
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity-solver > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity-solver > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import json
 d = json.load(open('gpurun_out/quick/bench.json'))

@@ -7,29 +7,29 @@ set -x
 export TMPDIR=/tmp
 R=${1:-r06}
 O=gpurun_out/refresh; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/${R}_bench_config2_lm.json 2> $O/bench_config2_lm.err
-python bench.py --solver trf --steps 5 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/${R}_bench_config2_trf.json 2>> $O/bench.err
-python bench.py --config 1 --no-cpu-baseline > $O/${R}_bench_config1_lm.json 2>> $O/bench.err
-python bench.py --config 4 --no-cpu-baseline > $O/${R}_bench_config4_calib_lm.json 2>> $O/bench.err
-python bench.py --config 3 --no-cpu-baseline --no-parity-solver > $O/${R}_bench_config3_one_gpu_lm.json 2>> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_config2_lm.json 2> $O/bench_config2_lm.err
+python bench.py --full --solver trf --steps 5 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/${R}_bench_config2_trf.json 2>> $O/bench.err
+python bench.py --full --config 1 --no-cpu-baseline > $O/${R}_bench_config1_lm.json 2>> $O/bench.err
+python bench.py --full --config 4 --no-cpu-baseline > $O/${R}_bench_config4_calib_lm.json 2>> $O/bench.err
+python bench.py --full --config 3 --no-cpu-baseline --no-parity-solver > $O/${R}_bench_config3_one_gpu_lm.json 2>> $O/bench.err
 # the opt_calib residual+Jacobian kernel (524 B/obs) at a size where a launch is not latency: configs[4]'s 7 cameras with 2M detections (1 GiB per launch)
-python bench.py --config 4 --obs 2000000 --steps 3 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/${R}_bench_config4_calib_2M_obs.json 2>> $O/bench.err
-rocprofv3 --kernel-trace --stats -d $O/stats_lm -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity-solver > $O/stats_lm.log 2>&1
+python bench.py --full --config 4 --obs 2000000 --steps 3 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/${R}_bench_config4_calib_2M_obs.json 2>> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/stats_lm -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity-solver > $O/stats_lm.log 2>&1
 python3 tools/rocprof_summary.py stats $O/stats_lm/r_results.db > $O/${R}_kernel_stats_config2_lm.txt
-rocprofv3 --kernel-trace --stats -d $O/stats_trf -o r -- python3 bench.py --solver trf --steps 5 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/stats_trf.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/stats_trf -o r -- python3 bench.py --full --solver trf --steps 5 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/stats_trf.log 2>&1
 python3 tools/rocprof_summary.py stats $O/stats_trf/r_results.db > $O/${R}_kernel_stats_config2_trf.txt
-rocprofv3 --kernel-trace --stats -d $O/stats_c3 -o r -- python3 bench.py --config 3 --no-cpu-baseline --no-parity-solver > $O/stats_c3.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/stats_c3 -o r -- python3 bench.py --full --config 3 --no-cpu-baseline --no-parity-solver > $O/stats_c3.log 2>&1
 python3 tools/rocprof_summary.py stats $O/stats_c3/r_results.db > $O/${R}_kernel_stats_config3_one_gpu_lm.txt
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity-solver > $O/pmc_fetch.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity-solver > $O/pmc_fetch.log 2>&1
 python3 tools/rocprof_summary.py pmc $O/pmc_fetch/r_results.db > $O/${R}_pmc_FETCH_SIZE_config2.txt
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write -o r -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity-solver > $O/pmc_write.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write -o r -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity-solver > $O/pmc_write.log 2>&1
 python3 tools/rocprof_summary.py pmc $O/pmc_write/r_results.db > $O/${R}_pmc_WRITE_SIZE_config2.txt
 python3 tools/rocprof_summary.py traffic $O/${R}_pmc_FETCH_SIZE_config2.txt $O/${R}_pmc_WRITE_SIZE_config2.txt config2_calib0 > $O/pmc_traffic_c2.json
 # configs[3] on one GPU (779 MB per launch of the judged kernel) and configs[4] (opt_calib: k_observations<true,true>)
 for C in 3 4; do
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch$C -o r -- python3 bench.py --config $C --steps 3 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/pmc_fetch$C.log 2>&1
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch$C -o r -- python3 bench.py --full --config $C --steps 3 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/pmc_fetch$C.log 2>&1
   python3 tools/rocprof_summary.py pmc $O/pmc_fetch$C/r_results.db > $O/${R}_pmc_FETCH_SIZE_config$C.txt
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write$C -o r -- python3 bench.py --config $C --steps 3 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/pmc_write$C.log 2>&1
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write$C -o r -- python3 bench.py --full --config $C --steps 3 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/pmc_write$C.log 2>&1
   python3 tools/rocprof_summary.py pmc $O/pmc_write$C/r_results.db > $O/${R}_pmc_WRITE_SIZE_config$C.txt
 done
 python3 tools/rocprof_summary.py traffic $O/${R}_pmc_FETCH_SIZE_config3.txt $O/${R}_pmc_WRITE_SIZE_config3.txt config3_calib0 $O/pmc_traffic_c2.json > $O/pmc_traffic_c23.json
@@ -65,7 +65,7 @@ ls -la $O
 bash tools/band_solver_ab.sh > $O/${R}_band_solver_ab.txt 2>/dev/null
 # round 6: the default solver on BASELINE configs[4] (opt_calib + rs_bounds + KE: the bounded TRF), the LM driver with and without the
 # speculative linearisation / carry-over (python wall, C++ wall, long solve), LM at configs[4] with the sequential driver for reference
-python bench.py --config 4 --solver trf --steps 3 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/${R}_bench_config4_calib_trf.json 2>> $O/bench.err
+python bench.py --full --config 4 --solver trf --steps 3 --warmup 1 --no-cpu-baseline --no-parity-solver > $O/${R}_bench_config4_calib_trf.json 2>> $O/bench.err
 ( python3 tools/micro/host_probe.py; echo "--- MVUS_NO_SPEC=1 MVUS_LM_NO_CARRY=1 (the sequential driver of rounds 2-5)"; MVUS_NO_SPEC=1 MVUS_LM_NO_CARRY=1 python3 tools/micro/host_probe.py ) 2>&1 | grep -v amdgpu > $O/${R}_lm_driver_spec_ab.txt
 # round 6: one rank of an 8-rank time-sharded run, alone on the GPU (per-kernel times behind the multi-GPU model of DESIGN section 6);
 # (window length, camera groups) sweep of the window-major assembly
