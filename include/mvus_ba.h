@@ -363,6 +363,31 @@ void mvus_spline_fit_close(mvus_spline_fit* fit);
 int mvus_pnp_ransac(int32_t device, int64_t N, const double* X, const double* uv, const double* K, const double* d, double reproj_error,
                     int32_t iterations, uint64_t seed, double* rvec, double* tvec, uint8_t* inliers, int64_t* n_inliers);
 
+/* cv2.findFundamentalMat(p1, p2, FM_RANSAC, thresh) (Scene.init_traj, common.py:193; synchronization.sync_bf, once per candidate
+ * time shift) for P independent problems in one call (epipolar.hip.h; OpenCV is absent from this image: parity unpinned).
+ * Problem p holds the pairs offsets[p] .. offsets[p+1]-1 of x1[2*Ntot], x2[2*Ntot] (u(Ntot) then v(Ntot); Ntot = offsets[P]),
+ * at least 8 of them.  `iterations` 7-point hypotheses per problem (OpenCV 4: at most 1000 at confidence 0.99; all are
+ * evaluated), drawn from `seed` by a counter-based sampler that depends only on (seed, hypothesis, problem size): a batched call
+ * and single calls give the same bits.  Score: pairs whose larger squared point-to-epipolar-line distance is <= thresh^2; the
+ * best model (ties: the lowest index) is refitted by the normalised 8-point algorithm on its inliers and the refit kept when it
+ * has at least as many inliers.  Outputs: F_out[9*P] (row-major, unit Frobenius norm, F[2][2] >= 0), mask[Ntot] (1 = inlier),
+ * n_inliers[P] (may be NULL).  MVUS_E_INVALID: fewer than 8 pairs in a problem, non-finite input, thresh <= 0, iterations outside
+ * 1..65536.  MVUS_E_NUMERIC: a problem has no valid 7-point model.  Stateless; no CPU fallback. */
+int mvus_fundamental_ransac(int32_t device, int32_t P, const int64_t* offsets, const double* x1, const double* x2, double thresh,
+                            int32_t iterations, uint64_t seed, double* F_out, uint8_t* mask, int32_t* n_inliers);
+
+/* cv2.correctMatches(F, p1, p2) (Scene.init_traj, common.py:206): the Hartley-Sturm optimal correction of N pairs under F[9]
+ * (row-major), x1[2*N], x2[2*N] -> x1c[2*N], x2c[2*N] in the same layout.  A pair with a non-finite coordinate comes back as
+ * NaN; no other pair does.  MVUS_E_INVALID: F not finite or zero.  Stateless; no CPU fallback. */
+int mvus_correct_matches(int32_t device, int64_t N, const double* F, const double* x1, const double* x2, double* x1c, double* x2c);
+
+/* epipolar.triangulate_from_E (epipolar.py:568-588) on normalised coordinates x1n[2*N], x2n[2*N] (K^-1 x, u(N) then v(N)):
+ * E[9] (row-major) decomposed into the four (R, t) of compute_Rt_from_E, each scored by sum(d1 > 0) + sum(d2 > 0) over the
+ * pairs triangulated with P1 = [I|0]; the first candidate to exceed the running maximum wins.  Outputs: P2_out[12] = [R|t]
+ * row-major, X_out[4*N] (x(N) y(N) z(N) w(N), w = 1) triangulated with it.  MVUS_E_INVALID: N < 1 or non-finite input.
+ * MVUS_E_NUMERIC: no candidate puts any point in front of a camera.  Stateless; no CPU fallback. */
+int mvus_pose_from_essential(int32_t device, int64_t N, const double* E, const double* x1n, const double* x2n, double* P2_out, double* X_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,10 @@ API = [
     ('mvus_pnp_ransac', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_int32,
                                        ctypes.c_uint64, c_double_p, c_double_p, c_uint8_p, c_int64_p]),
     ('mvus_triangulate', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ('mvus_fundamental_ransac', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_int32,
+                                               ctypes.c_uint64, c_double_p, c_uint8_p, c_int32_p]),
+    ('mvus_correct_matches', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ('mvus_pose_from_essential', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
 ]
 
 _lib = None

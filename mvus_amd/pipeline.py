@@ -1,11 +1,15 @@
-"""The incremental reconstruction loop of the reference's ``main.py`` (lines 43-82) over the drop-in ``Scene``: for the
-current number of cameras BA -> remove_outliers -> BA, then -- until every camera is in -- select_most_overlap ->
-get_camera_pose -> triangulate (with the spline refit).  Every stage runs on the GPU through libmvusba.so; this module only
-sequences them (same order, same settings keys) and keeps a wall-clock split per stage.
+"""The reference's ``main.py`` over the drop-in ``Scene``.  ``reconstruct_from_config`` runs all of it (lines 18-93) from a
+config.json on disk: create_scene -> cut_detection -> init_alpha -> time_shift -> detection_to_global -> init_traj ->
+traj_to_spline, then the incremental loop, spline_to_traj, align_gt when ground truth is given, and the output pickle.
+``incremental_reconstruction`` is the loop alone (lines 43-82): for the current number of cameras BA -> remove_outliers -> BA,
+then -- until every camera is in -- select_most_overlap -> get_camera_pose -> triangulate (with the spline refit).  Every stage
+with arithmetic to speak of runs on the GPU through libmvusba.so; this module only sequences them (same order, same settings
+keys) and keeps a wall-clock split per stage (``StageTimer``).
 
-Out of scope stays out of scope: the start of the loop -- two cameras with poses and a first trajectory, which the reference
-gets from ``init_traj`` (epipolar geometry) -- is an input here.
+    python -m mvus_amd.pipeline config.json
 """
+import pickle
+import sys
 import time
 
 import numpy as np
@@ -179,3 +183,44 @@ def evaluate_against_truth(flight, sc):
         out['rot_err_deg'].append(float(np.degrees(np.arccos(np.clip(0.5 * (np.trace(Rrel) - 1.0), -1.0, 1.0)))))
     out['trajectory_extent'] = (float(flight.spline['int'][0, 0]), float(flight.spline['int'][1, -1]), float(sc.interval[1, -1]))
     return out
+
+
+def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output=True):
+    """main.py:18-93 from the config.json at ``path`` (the reference's schema; ``create_scene``): every stage through
+    ``StageTimer`` -- create_scene, cut_detection, init_alpha, time_shift, detection_to_global, init_traj(error=thres_Fmatix),
+    traj_to_spline, the incremental loop, spline_to_traj; ``align_gt`` when the config gives ground truth; the Scene pickled to
+    ``settings['path_output']`` when ``output`` and that key is set.  Returns (Scene, StageTimer)."""
+    from .reconstruction import common
+    timer = timer or StageTimer()
+    flight = timer.run('create_scene', 0, common.create_scene, str(path))
+    st = flight.settings
+    timer.run('cut_detection', 0, flight.cut_detection, second=st.get('cut_detection_second', 0))
+    timer.run('init_alpha', 0, flight.init_alpha)
+    timer.run('time_shift', 0, flight.time_shift)
+    timer.run('detection_to_global', 0, flight.detection_to_global)
+    timer.run('init_traj', 2, flight.init_traj, error=st.get('thres_Fmatix', 10))
+    timer.run('traj_to_spline', 2, flight.traj_to_spline, smooth_factor=st['smooth_factor'])
+    incremental_reconstruction(flight, max_iter=max_iter, verbose=verbose, timer=timer)
+    flight.out = {'reconst_tran': flight.traj[1:]}
+    if flight.gt:
+        from .analysis.compare_gt import align_gt
+        flight.out = timer.run('align_gt', flight.numCam, align_gt, flight, flight.gt['frequency'], flight.gt['filepath'], visualize=False)
+    if output and st.get('path_output'):
+        with open(st['path_output'], 'wb') as fh:
+            pickle.dump(flight, fh)
+    return flight, timer
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    if len(argv) < 1:
+        print('Please provide a path to a proper config file')
+        return 1
+    _, timer = reconstruct_from_config(argv[0], verbose=True)
+    print('seconds per stage:', {k: round(v, 3) for k, v in timer.totals().items()})
+    print('Finished!')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -7,9 +7,10 @@ Kept from the reference: the ``Scene`` attribute set that ends up in the output 
 method names and signatures, the ``config.json`` schema (``create_scene``), the parameter-vector layout and the
 side effects of ``BA`` on ``alpha/beta/rs/cameras/spline/detections_global``.
 
-Out of scope: trajectory initialisation, PnP-RANSAC, synchronisation search, plotting, and the
-dead ``motion_prior=True`` branch -- those methods raise ``NotImplementedError``.  ``Scene.triangulate`` (SURVEY 8f rank
-4) is here, with its per-point SVD on the GPU.
+Also on the GPU: ``Scene.init_traj`` (two-view initialisation: fundamental matrix by RANSAC, optimal correction, pose from
+E), ``Scene.time_shift`` with ``cf_exact: false`` and ``sync_method: 'bf'`` (synchronization.sync_bf), ``get_camera_pose`` (PnP +
+RANSAC) and ``Scene.triangulate`` (per-point SVD).  Out of scope: ``sync_iter``, plotting, and the dead ``motion_prior=True``
+branch -- those raise ``NotImplementedError``.
 
 Extra ``settings`` keys (all optional; a reference ``config.json`` has none of them):
 
@@ -200,7 +201,27 @@ class Scene:
             self.beta = self.cf[self.ref_cam] - self.alpha * self.cf
             print('The given corresponding frames are directly exploited as temporal synchronization\n')
         else:
-            raise NotImplementedError('synchronisation search (sync_iter / sync_bf) is outside the BA hot path')
+            # common.py:1016-1040: the brute-force search of synchronization.sync_bf against the reference camera, each of its
+            # two stages one batched RANSAC call on the GPU
+            from . import synchronization as sync
+            method = self.settings.get('sync_method')
+            if method == 'iter':
+                sync_fun = sync.sync_iter
+            elif method == 'bf':
+                sync_fun = sync.sync_bf
+            else:
+                raise ValueError('Synchronization method must be either "iter" or "bf"')
+            device = int(self.settings.get('device', 0))
+            print('Computing temporal synchronization...\n')
+            beta = np.zeros(self.numCam)
+            i = self.ref_cam
+            for j in range(self.numCam):
+                if j != i:
+                    beta[j], _ = sync_fun(self.cameras[i].fps, self.cameras[j].fps, self.detections[i], self.detections[j],
+                                          self.cf[i], self.cf[j], device=device)
+                print('Status: {} from {} cam finished'.format(j + 1, self.numCam))
+            self.beta = beta
+            self.beta_after_Fbeta = beta.copy()
 
     def detection_to_global(self, *cam, motion_prior=False):
         """Frame indices -> global timeline, and the observed pixel (common.py:105-127)."""
@@ -600,7 +621,41 @@ class Scene:
         raise NotImplementedError('outside the BA hot path this package accelerates (SURVEY.md section 2); '
                                   'use the reference implementation for initialisation / synchronisation search')
 
-    init_traj = plot_reprojection = _out_of_scope
+    plot_reprojection = _out_of_scope
+
+    def init_traj(self, error=10, inlier_only=False):
+        """The first two cameras and the first trajectory (reference common.py:178-221): the pair with the most overlap, F by
+        RANSAC on their matched detections (``mvus_fundamental_ransac``), E = K2^T F K1, the optimal correction of the pairs
+        (``mvus_correct_matches``), the pose of the second camera and the points from E (``mvus_pose_from_essential``).  With
+        ``inlier_only=False`` every pair is kept, as in the reference.  A scene with fewer than two cameras has no pair to start
+        from: single-view reconstruction is not implemented (the reference fails there with a TypeError on ``sequence``)."""
+        from . import epipolar as ep
+        if len(self.cameras) < 2 or self.numCam < 2:
+            raise NotImplementedError('init_traj: two-view initialisation needs at least two cameras with detections (this scene has '
+                                      '%d); single-view reconstruction is not implemented' % min(len(self.cameras), self.numCam))
+        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
+        self.select_most_overlap(init=True)
+        t1, t2 = self.sequence[0], self.sequence[1]
+        K1, K2 = self.cameras[t1].K, self.cameras[t2].K
+        if self.cameras[t1].fps > self.cameras[t2].fps:          # the denser camera first in match_overlap
+            d1, d2 = util.match_overlap(self.detections_global[t1], self.detections_global[t2])
+        else:
+            d2, d1 = util.match_overlap(self.detections_global[t2], self.detections_global[t1])
+        F, inlier = ep.computeFundamentalMat(d1[1:], d2[1:], error=error, device=device)
+        E = K2.T @ F @ K1
+        if not inlier_only:
+            inlier = np.ones(len(inlier))
+        keep = inlier == 1
+        m1, m2 = ep.correct_matches(F, d1[1:, keep], d2[1:, keep], device=device)
+        x1, x2 = util.homogeneous(m1), util.homogeneous(m2)
+        mask = np.logical_not(np.isnan(x1[0]))
+        x1, x2 = x1[:, mask], x2[:, mask]
+        X, P = ep.triangulate_from_E(E, K1, K2, x1, x2, device=device)
+        self.traj = np.vstack((d1[0][keep][mask], X[:-1]))
+        self.cameras[t1].P = K1 @ np.hstack((np.eye(3), np.zeros((3, 1))))
+        self.cameras[t2].P = K2 @ P
+        self.cameras[t1].decompose()
+        self.cameras[t2].decompose()
 
     def error_motion(self, cams, mode='dist', norm=False, motion_weights=0, motion_reg=False, motion_prior=False):
         """The motion-regularisation rows of the BA residual (reference common.py:362-424 with ``motion_reg=True``): one value
