@@ -13,7 +13,7 @@
 //     k_fm_hypotheses  one lane per (problem, hypothesis): 7 distinct indices from the counter-based sampler fm_sample7 (the
 //                      same draw on the host and in a batched or single call), the 7-point algorithm in normalised
 //                      coordinates -- the 2-D null space of the 7x9 system by Gauss-Jordan elimination with full pivoting,
-//                      then the real roots of the cubic det(l F1 + (1-l) F2) -- and up to 3 denormalised models; empty
+//                      then the real roots of the cubic det(l F1 + (1-l) F2) (fm_cubic_roots) -- and up to 3 denormalised models; empty
 //                      slots are marked invalid.  All hypotheses are evaluated: there is no adaptive early stop.
 //     k_fm_score       one lane per model, the problem's pairs streamed through LDS in tiles (broadcast reads); the inlier
 //                      count stays in a register, so no reduction.  fp64 with contraction off: the count is the oracle's.
@@ -34,6 +34,7 @@
 //   of each camera counted as per-block integer partials.  The winner is chosen on the host exactly as the reference does
 //   (first candidate whose count exceeds the running maximum) and triangulated with k_triangulate.
 #pragma once
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 
@@ -101,51 +102,102 @@ MVUS_HD void fm_denormalise(const double* Fn, const double* norm, double* F) {
   for (int a = 0; a < 9; ++a) F[a] *= sc;
 }
 
-// real roots of c3 l^3 + c2 l^2 + c1 l + c0 (at most 3), each polished by two Newton steps
-MVUS_HD int fm_cubic_roots(double c3, double c2, double c1, double c0, double* r) {
-  const double mx = fmax(fmax(fabs(c3), fabs(c2)), fmax(fabs(c1), fabs(c0)));
-  if (!(mx > 0.0)) return 0;
-  int n = 0;
-  if (fabs(c3) <= 1e-12 * mx) {
-    if (fabs(c2) <= 1e-12 * mx) {
-      if (fabs(c1) <= 1e-12 * mx) return 0;
-      r[n++] = -c0 / c1;
-    } else {
-      const double disc = c1 * c1 - 4.0 * c2 * c0;
-      if (disc < 0.0) return 0;
-      const double q = -0.5 * (c1 + (c1 >= 0.0 ? sqrt(disc) : -sqrt(disc)));
-      r[n++] = q / c2;
-      if (q != 0.0) r[n++] = c0 / q;
-    }
-  } else {
-    const double a = c2 / c3, b = c1 / c3, c = c0 / c3;
-    const double Q = (a * a - 3.0 * b) / 9.0, R = (2.0 * a * a * a - 9.0 * a * b + 27.0 * c) / 54.0;
-    const double Q3 = Q * Q * Q;
-    if (R * R < Q3) {
-      const double th = acos(fmin(1.0, fmax(-1.0, R / sqrt(Q3)))), sq = -2.0 * sqrt(Q);
-      r[0] = sq * cos(th / 3.0) - a / 3.0;
-      r[1] = sq * cos((th + 2.0 * M_PI) / 3.0) - a / 3.0;
-      r[2] = sq * cos((th - 2.0 * M_PI) / 3.0) - a / 3.0;
-      n = 3;
-    } else {
-      double A = cbrt(fabs(R) + sqrt(R * R - Q3));
-      if (R > 0.0) A = -A;
-      const double B = A != 0.0 ? Q / A : 0.0;
-      r[0] = A + B - a / 3.0;
-      n = 1;
-    }
-  }
+MVUS_HD double fm_cubic_eval(double c3, double c2, double c1, double c0, double x) { return ((c3 * x + c2) * x + c1) * x + c0; }
+
+// Real roots of q2 x^2 + q1 x + q0 (q2 != 0) by the stable formula.  A discriminant within 16 eps (q1^2 + 4 |q2 q0|) of zero --
+// a bound on its own rounding error -- is a double root -q1 / (2 q2), returned once.  The coefficients are first scaled by a
+// power of two (exact: the same bits wherever nothing under- or overflows) so that the largest is in [1, 2): the squares can
+// neither underflow nor overflow.
+MVUS_HD int fm_quadratic_roots(double q2, double q1, double q0, double* r) {
+  const int e = ilogb(fmax(fabs(q2), fmax(fabs(q1), fabs(q0))));
+  q2 = ldexp(q2, -e); q1 = ldexp(q1, -e); q0 = ldexp(q0, -e);
+  const double disc = q1 * q1 - 4.0 * q2 * q0, tol = 16.0 * DBL_EPSILON * (q1 * q1 + 4.0 * fabs(q2 * q0));
+  if (disc < -tol) return 0;
+  if (disc <= tol) { r[0] = -0.5 * q1 / q2; return 1; }
+  const double q = -0.5 * (q1 + (q1 >= 0.0 ? sqrt(disc) : -sqrt(disc)));
+  r[0] = q / q2;
+  if (q == 0.0) return 1;
+  r[1] = q0 / q;
+  return 2;
+}
+
+// two Newton steps on each of r[0..n), a step kept only when it does not increase |cubic| (near a double root f' is rounding
+// noise and an unguarded step can jump off the pair)
+MVUS_HD void fm_cubic_polish(double c3, double c2, double c1, double c0, double* r, int n) {
   for (int k = 0; k < n; ++k)
     for (int it = 0; it < 2; ++it) {
       const double x = r[k];
-      const double f = ((c3 * x + c2) * x + c1) * x + c0, df = (3.0 * c3 * x + 2.0 * c2) * x + c1;
-      if (df != 0.0) { const double xn = x - f / df; if (fm_finite(xn)) r[k] = xn; }
+      const double f = fm_cubic_eval(c3, c2, c1, c0, x), df = (3.0 * c3 * x + 2.0 * c2) * x + c1;
+      if (df == 0.0) break;
+      const double xn = x - f / df;
+      if (!fm_finite(xn) || !(fabs(fm_cubic_eval(c3, c2, c1, c0, xn)) <= fabs(f))) break;
+      r[k] = xn;
     }
-  return n;
+}
+
+// Real roots of c3 l^3 + c2 l^2 + c1 l + c0 (at most 3).  |c3| <= 1e-12 max|c|: the quadratic (or linear) polynomial.  Otherwise
+// one real root x0 by the closed form -- the largest in magnitude of the three of the trigonometric formula when R^2 < Q^3, else
+// A + B - a/3 -- polished, then the cubic deflated by it (from the constant term when x0 is the largest root in magnitude, from
+// the leading term otherwise) and the quadratic's roots by fm_quadratic_roots.  The closed form alone loses roots: a double or
+// near-double pair that rounding moves to the R^2 >= Q^3 side, and the small roots next to a huge one (|c3| just above the
+// cutoff), where cancellation against a/3 leaves no correct digit.  Every root is polished by fm_cubic_polish.
+//
+// delta: the absolute uncertainty of the coefficients (0: exact).  When the deflated quadratic has a complex pair m +- i y and m
+// is a root of the cubic to within that uncertainty, |cubic(m)| <= delta (|m|^3 + |m|^2 + |m| + 1), the pair is a double root
+// split by the coefficients' errors (|y| ~ sqrt(delta)), and m is returned as one root.
+MVUS_HD int fm_cubic_roots(double c3, double c2, double c1, double c0, double* r, double delta = 0.0) {
+  const double mx = fmax(fmax(fabs(c3), fabs(c2)), fmax(fabs(c1), fabs(c0)));
+  if (!(mx > 0.0)) return 0;
+  if (fabs(c3) <= 1e-12 * mx) {
+    if (fabs(c2) <= 1e-12 * mx) {
+      if (fabs(c1) <= 1e-12 * mx) return 0;
+      r[0] = -c0 / c1;
+      fm_cubic_polish(c3, c2, c1, c0, r, 1);
+      return 1;
+    }
+    const int n = fm_quadratic_roots(c2, c1, c0, r);
+    fm_cubic_polish(c3, c2, c1, c0, r, n);
+    return n;
+  }
+  const double a = c2 / c3, b = c1 / c3, c = c0 / c3;
+  const double Q = (a * a - 3.0 * b) / 9.0, R = (2.0 * a * a * a - 9.0 * a * b + 27.0 * c) / 54.0;
+  const double Q3 = Q * Q * Q;
+  double x0;
+  if (R * R < Q3) {
+    const double th = acos(fmin(1.0, fmax(-1.0, R / sqrt(Q3)))), sq = -2.0 * sqrt(Q);
+    x0 = sq * cos(th / 3.0) - a / 3.0;
+    const double t1 = sq * cos((th + 2.0 * M_PI) / 3.0) - a / 3.0, t2 = sq * cos((th - 2.0 * M_PI) / 3.0) - a / 3.0;
+    if (fabs(t1) > fabs(x0)) x0 = t1;
+    if (fabs(t2) > fabs(x0)) x0 = t2;
+  } else {
+    double A = cbrt(fabs(R) + sqrt(R * R - Q3));
+    if (R > 0.0) A = -A;
+    const double B = A != 0.0 ? Q / A : 0.0;
+    x0 = A + B - a / 3.0;
+  }
+  r[0] = x0;
+  fm_cubic_polish(c3, c2, c1, c0, r, 1);
+  x0 = r[0];
+  double q1, q0;
+  if (x0 != 0.0 && fabs(x0) * x0 * x0 * fabs(c3) >= fabs(c0)) { q0 = -c0 / x0; q1 = (q0 - c1) / x0; }
+  else { q1 = c2 + c3 * x0; q0 = c1 + q1 * x0; }
+  int m = fm_quadratic_roots(c3, q1, q0, r + 1);
+  if (m == 0 && delta > 0.0) {
+    const double xm = -0.5 * (q1 / c3), ax = fabs(xm);
+    if (fabs(fm_cubic_eval(c3, c2, c1, c0, xm)) <= delta * (((ax + 1.0) * ax + 1.0) * ax + 1.0)) { r[1] = xm; m = 1; }
+  }
+  fm_cubic_polish(c3, c2, c1, c0, r + 1, m);
+  return 1 + m;
 }
 
 MVUS_HD double fm_det3(const double* A) {
   return A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
+}
+
+MVUS_HD double fm_perm3_abs(const double* A) {
+  const double a0 = fabs(A[0]), a1 = fabs(A[1]), a2 = fabs(A[2]), a3 = fabs(A[3]), a4 = fabs(A[4]), a5 = fabs(A[5]);
+  const double a6 = fabs(A[6]), a7 = fabs(A[7]), a8 = fabs(A[8]);
+  return a0 * (a4 * a8 + a5 * a7) + a1 * (a3 * a8 + a5 * a6) + a2 * (a3 * a7 + a4 * a6);
 }
 
 // The 7-point algorithm on normalised pairs xs[7][4] = (x1 y1 x2 y2): up to 3 normalised models Fs[k][9]; returns their number.
@@ -185,16 +237,19 @@ MVUS_HD int fm_seven_point(const double (*xs)[4], double (*Fs)[9]) {
   F1[perm[7]] = 1.0; F1[perm[8]] = 0.0;
   F2[perm[7]] = 0.0; F2[perm[8]] = 1.0;
   // det(l F1 + (1 - l) F2) = c3 l^3 + c2 l^2 + c1 l + c0 from its values at l = 0, 1, -1, 2
-  double M[9], dv[4];
+  // delta: a bound on the coefficients' rounding errors, 128 eps times the largest permanent of |M| (the size of the terms of
+  // the determinants) -- a double root of the exact sample must not be lost to them
+  double M[9], dv[4], pmax = 0.0;
   const double ls[4] = {0.0, 1.0, -1.0, 2.0};
   for (int q = 0; q < 4; ++q) {
     for (int a = 0; a < 9; ++a) M[a] = ls[q] * F1[a] + (1.0 - ls[q]) * F2[a];
     dv[q] = fm_det3(M);
+    pmax = fmax(pmax, fm_perm3_abs(M));
   }
   const double c0 = dv[0], c2 = 0.5 * (dv[1] + dv[2]) - c0, s = 0.5 * (dv[1] - dv[2]);
   const double c3 = (dv[3] - 4.0 * c2 - c0 - 2.0 * s) / 6.0, c1 = s - c3;
   double roots[3];
-  const int nr = fm_cubic_roots(c3, c2, c1, c0, roots);
+  const int nr = fm_cubic_roots(c3, c2, c1, c0, roots, 128.0 * DBL_EPSILON * pmax);
   int n = 0;
   for (int k = 0; k < nr; ++k) {
     const double l = roots[k];

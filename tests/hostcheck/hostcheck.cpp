@@ -5,6 +5,7 @@
 #include "../../mvus_amd/csrc/triangulate.hip.h"
 #include "../../mvus_amd/csrc/spline_fit.hip.h"
 #include "../../mvus_amd/csrc/pnp.hip.h"
+#include "../../mvus_amd/csrc/epipolar.hip.h"
 
 using namespace mvus;
 
@@ -100,3 +101,13 @@ extern "C" int hostcheck_pnp_point_normal(const double* K, const double* d, cons
 }
 extern "C" void hostcheck_pnp_sample6(unsigned long long seed, int h, long long N, long long* idx) { pnp_sample6(seed, h, N, idx); }
 extern "C" void hostcheck_rotation_to_rvec(const double* R, double* r) { rotation_to_rvec(R, r); }
+
+// host build of the two-view math (mvus_amd/csrc/epipolar.hip.h)
+extern "C" int hostcheck_fm_cubic_roots(const double* c /* c3 c2 c1 c0 */, double* r) { return fm_cubic_roots(c[0], c[1], c[2], c[3], r); }
+extern "C" int hostcheck_fm_seven_point(const double* xs /* [7][4] */, double* Fs /* [3][9] */) {
+  return fm_seven_point(reinterpret_cast<const double (*)[4]>(xs), reinterpret_cast<double (*)[9]>(Fs));
+}
+// x1, x2: [2][N]; err[N]
+extern "C" void hostcheck_fm_error(long long N, const double* F, const double* x1, const double* x2, double* err) {
+  for (long long i = 0; i < N; ++i) err[i] = fm_error(F, x1[i], x1[N + i], x2[i], x2[N + i]);
+}

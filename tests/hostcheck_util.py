@@ -10,7 +10,7 @@ from mvus_amd import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = [os.path.join(HERE, 'hostcheck', f) for f in ('hostcheck.cpp', 'host_backend.cpp')]
-DEPS = SRC + [os.path.join(ROOT, 'mvus_amd', 'csrc', f) for f in ('ba_math.h', 'ba_solver.h', 'ba_problem.h', 'ba_schur.h', 'ba_partition.h', 'triangulate.hip.h', 'spline_fit.hip.h', 'pnp.hip.h')] \
+DEPS = SRC + [os.path.join(ROOT, 'mvus_amd', 'csrc', f) for f in ('ba_math.h', 'ba_solver.h', 'ba_problem.h', 'ba_schur.h', 'ba_partition.h', 'triangulate.hip.h', 'spline_fit.hip.h', 'pnp.hip.h', 'epipolar.hip.h')] \
     + [os.path.join(ROOT, 'include', 'mvus_ba.h')]
 SO = os.path.join(HERE, 'hostcheck', 'libhostcheck.so')
 
@@ -55,6 +55,9 @@ def load():
     lib.hostcheck_pnp_point_normal.argtypes = [_lib.c_double_p] * 5 + [ctypes.c_double, ctypes.c_double, _lib.c_double_p]
     lib.hostcheck_pnp_sample6.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_longlong, _lib.c_int64_p]
     lib.hostcheck_rotation_to_rvec.argtypes = [_lib.c_double_p, _lib.c_double_p]
+    lib.hostcheck_fm_cubic_roots.argtypes = [_lib.c_double_p, _lib.c_double_p]
+    lib.hostcheck_fm_seven_point.argtypes = [_lib.c_double_p, _lib.c_double_p]
+    lib.hostcheck_fm_error.argtypes = [ctypes.c_longlong] + [_lib.c_double_p] * 4
     _cached = lib
     return lib
 
