@@ -148,7 +148,7 @@ void mvus_default_opts(mvus_solve_opts* opts);
  * binding asserts these against its own struct definitions at load time -- mvus_solve_opts has grown over the rounds (lm_lambda_min,
  * lm_trust_radius) and a stale stub would otherwise hand the library a short buffer.  The version is raised whenever a struct or a
  * prototype of this header changes.  Stateless, no device is touched.  No reference counterpart (the reference has no FFI). */
-#define MVUS_ABI_VERSION 7
+#define MVUS_ABI_VERSION 8
 int32_t mvus_abi_sizes(int32_t* solve_opts_size, int32_t* result_size, int32_t* problem_size);
 
 /* Copies the problem to the GPU, undistorts observations once when calibration is fixed
@@ -242,6 +242,28 @@ int mvus_ba_normal_equations(mvus_ba* h, double* g, double* JtJ_cam, double* ban
  * (assembly, band solver, Schur complement, reduced system); no trial evaluation, no bounds.  No reference counterpart. */
 int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out);
 
+/* Robust loss: least_squares(..., loss=, f_scale=) of common.py:670 (the reference passes neither: linear, 1.0).  With z = (f_i / f_scale)^2
+ * for EVERY row of f (motion rows included, as scipy does with error_BA):
+ *   MVUS_LOSS_LINEAR rho = z | SOFT_L1 2 (sqrt(1 + z) - 1) | HUBER z if z <= 1 else 2 sqrt(z) - 1 | CAUCHY log(1 + z) | ARCTAN atan(z)
+ *   cost = 0.5 f_scale^2 sum rho(z_i)  (mvus_result cost, initial_cost, the gain ratio of every trial);
+ *   linearisation = scipy's scale_for_robust_loss_function: J_i <- s_i J_i, f_i <- rho' f_i / s_i, s_i = sqrt(max(rho' + 2 rho'' z, 2.22e-16)),
+ *   i.e. g = J^T (rho' f), H = J^T diag(s^2) J, damping diag(H) of that H; optimality = |g|_inf of that g.
+ * In force for every later mvus_ba_solve / mvus_ba_normal_equations / mvus_ba_lm_step on the handle until set again; everything about
+ * error_BA itself (residual, Jacobian, J v, J^T u, motion rows, outlier masks, f_out of a solve) stays raw.  Setting a loss drops what
+ * an earlier LM solve carried over (cost, normal equations) and, when the loss changes, the damping history.
+ * MVUS_E_INVALID: unknown loss, f_scale not finite or <= 0.  With a loss other than linear mvus_ba_solve returns MVUS_E_UNSUPPORTED for
+ * MVUS_SOLVER_TRF_LSMR, for a Jacobian mode other than MVUS_JAC_ANALYTIC and on sharded handles -- it never solves the linear problem
+ * instead. */
+#define MVUS_LOSS_LINEAR 0
+#define MVUS_LOSS_SOFT_L1 1
+#define MVUS_LOSS_HUBER 2
+#define MVUS_LOSS_CAUCHY 3
+#define MVUS_LOSS_ARCTAN 4
+int mvus_ba_set_loss(mvus_ba* h, int32_t loss, double f_scale);
+/* 0.5 f_scale^2 sum rho((f_i / f_scale)^2) at x under the loss in force; weights_out[m] (may be NULL) = rho'(z_i), the weight each row
+ * has in the gradient (1 = inlier, -> 0 = ignored), in the row order of f.  One rank only. */
+int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* weights_out);
+
 /* The least_squares call of Scene.BA (common.py:670) -- x is read and overwritten with res.x.
  * lb/ub come from opts of the problem (rs_bounds).  f_out[m] may be NULL.  x, res and f_out are complete on return.  MVUS_SOLVER_LM_SCHUR
  * with f_out == NULL may return while device work for the NEXT call is still running on the handle's stream (the linearisation at the
@@ -298,7 +320,8 @@ int mvus_ba_set_time_shard(mvus_ba* h, int32_t rank, int32_t world, const int32_
 
 /* Measurement hook for bench.py: runs `launches` back-to-back launches of one kernel on the handle's
  * stream between two hipEvents and returns the average duration in milliseconds.
- *   which: 0 residual, 1 residual+Jacobian with the outputs ROTATING over >= 3 buffer sets (>= 1 GiB in rotation, so no
+ *   which: 0 residual (with a loss other than linear in force: the whole cost evaluation of a robust LM trial -- residual kernel with
+ *   the robust partial sums, motion rows and the final sum), 1 residual+Jacobian with the outputs ROTATING over >= 3 buffer sets (>= 1 GiB in rotation, so no
  *   launch writes into lines its predecessor left in the 256 MiB Infinity Cache), 2 J v, 3 J^T u, 4 normal-equation
  *   assembly from the materialised Jacobian, 5 residual+Jacobian re-launched into one buffer set (cache-resident variant,
  *   for comparison), 6 the fused Jacobian + normal-equation assembly of the LM path (no Jacobian in memory) */

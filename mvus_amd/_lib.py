@@ -16,6 +16,8 @@ MVUS_E_INVALID, MVUS_E_HIP, MVUS_E_NUMERIC, MVUS_E_COMM, MVUS_E_UNSUPPORTED, MVU
 JAC_ANALYTIC, JAC_PATTERN, JAC_FD = 0, 1, 2
 PAT_SHIFT, PAT_TIE = 25, 1 << 30          # pattern codes of mvus_ba_set_pattern (include/mvus_ba.h)
 SOLVER_TRF_LSMR, SOLVER_LM_SCHUR = 0, 1
+LOSS_LINEAR, LOSS_SOFT_L1, LOSS_HUBER, LOSS_CAUCHY, LOSS_ARCTAN = 0, 1, 2, 3, 4      # mvus_ba_set_loss
+LOSS_NAMES = {'linear': LOSS_LINEAR, 'soft_l1': LOSS_SOFT_L1, 'huber': LOSS_HUBER, 'cauchy': LOSS_CAUCHY, 'arctan': LOSS_ARCTAN}
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -81,6 +83,8 @@ API = [
     ('mvus_ba_jtu', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p]),
     ('mvus_ba_normal_equations', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
     ('mvus_ba_lm_step', ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p]),
+    ('mvus_ba_set_loss', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
+    ('mvus_ba_robust_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
     ('mvus_ba_solve', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.POINTER(MvusSolveOpts), ctypes.POINTER(MvusResult), c_double_p]),
     ('mvus_ba_outlier_mask', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_uint8_p]),
     ('mvus_ba_remove_outliers', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_uint8_p, c_int64_p]),
@@ -141,7 +145,7 @@ def load(path=None):
     return lib
 
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 def check_abi(lib):

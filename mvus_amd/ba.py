@@ -13,6 +13,18 @@ import numpy as np
 
 from . import _lib
 from ._lib import JAC_ANALYTIC, JAC_FD, JAC_PATTERN, SOLVER_LM_SCHUR, SOLVER_TRF_LSMR  # noqa: F401 (re-exported)
+from ._lib import LOSS_ARCTAN, LOSS_CAUCHY, LOSS_HUBER, LOSS_LINEAR, LOSS_NAMES, LOSS_SOFT_L1  # noqa: F401 (re-exported)
+
+
+def loss_code(loss):
+    """'linear' | 'soft_l1' | 'huber' | 'cauchy' | 'arctan' (scipy's names) or an integer MVUS_LOSS_* code -> the code.  An unknown
+    NAME raises ValueError here; an unknown integer is left to the library (MVUS_E_INVALID)."""
+    if isinstance(loss, str):
+        if loss not in LOSS_NAMES:
+            raise ValueError('unknown loss %r: one of %s' % (loss, ', '.join(sorted(LOSS_NAMES))))
+        return LOSS_NAMES[loss]
+    return int(loss)
+
 
 class UnsupportedBySolver(RuntimeError):
     """MVUS_E_UNSUPPORTED: the problem is outside what the chosen solver handles (see include/mvus_ba.h); the other solver has no such limit."""
@@ -53,6 +65,7 @@ class BAHandle:
         self.NS = int(self.lib.mvus_ba_num_slots(h))
         self.M = prob.M
         self._cb = None
+        self.loss = (LOSS_LINEAR, 1.0)     # (code, f_scale) in force: set_loss
 
     def close(self):
         if getattr(self, 'h', None):
@@ -210,6 +223,23 @@ class BAHandle:
         p = np.empty(self.n)
         self._check(self.lib.mvus_ba_lm_step(self.h, float(lam), _lib.dptr(p)), 'mvus_ba_lm_step')
         return p
+
+    def set_loss(self, loss, f_scale=1.0):
+        """least_squares(loss=, f_scale=): the robust loss of every later solve / normal_equations / lm_step on the handle (LM + Schur,
+        analytic Jacobian, one rank).  residual, residual_jacobian, jv, jtu and the outlier masks stay those of error_BA."""
+        code = loss_code(loss)
+        self._check(self.lib.mvus_ba_set_loss(self.h, code, float(f_scale)), 'mvus_ba_set_loss')
+        self.loss = (code, float(f_scale))
+
+    def robust_cost(self, x, weights=False):
+        """0.5 f_scale^2 sum rho((f_i / f_scale)^2) at x under the loss in force; with ``weights`` also rho' of every row of f
+        (1 = inlier, -> 0 = ignored): (cost, w[m])."""
+        x = self._x(x, self.n)
+        cost = ctypes.c_double(0.0)
+        w = np.empty(self.m) if weights else None
+        self._check(self.lib.mvus_ba_robust_cost(self.h, _lib.dptr(x), ctypes.byref(cost), _lib.dptr(w) if weights else None),
+                    'mvus_ba_robust_cost')
+        return (cost.value, w) if weights else cost.value
 
     def solve(self, x0, solver=SOLVER_TRF_LSMR, jac_mode=JAC_PATTERN, max_nfev=10, opts=None, return_fun=True,
               ties='numpy', matrix=None, prepared=False):

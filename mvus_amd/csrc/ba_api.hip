@@ -500,6 +500,11 @@ struct HipBackend {
     for (int w = 0; w < kThreads / 64; ++w) t += red[w];
     return t;
   }
+  // The loss in force (mvus_ba_set_loss; kind 0 = linear).  With another kind the partial sums below are those of f_scale^2 rho(z) -- the
+  // LM driver's cost, trial cost and gain ratio are the robust ones with no change to the driver -- and HipSchur's assembly kernels scale
+  // the rows as they read them; f in memory is the raw error_BA throughout.  (Sharded handles refuse a loss: mvus_ba_solve.)
+  LossSpec loss{0, 1.0};
+  bool robust() const { return loss.kind != 0; }
   // clr / clr_len: storage to zero beside the evaluation (HipSchur's normal-equation blocks); returns false if it was not done
   bool residual_sq(const double* x, double* f, double* out, double* clr = nullptr, int64_t clr_len = 0) {
     // (observation shards off the root rank: the replicated motion rows are rows of zeros there -- the general path)
@@ -527,12 +532,18 @@ struct HipBackend {
       const int fb = (clr && clr_len > 0) ? (int)std::min<int64_t>(2048, (clr_len + kThreads - 1) / kThreads) : 0;
       const dim3 g(dp.n_chunks + fb), b(kThreads);
       double* c = fb > 0 ? clr : (double*)nullptr;
-      if (hp.calib) hipLaunchKernelGGL((k_observations<true, false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len);
-      else hipLaunchKernelGGL((k_observations<false, false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len);
+      if (robust()) {
+        if (hp.calib) hipLaunchKernelGGL((k_observations<true, false, true>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len, loss);
+        else hipLaunchKernelGGL((k_observations<false, false, true>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len, loss);
+      } else {
+        if (hp.calib) hipLaunchKernelGGL((k_observations<true, false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len);
+        else hipLaunchKernelGGL((k_observations<false, false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len);
+      }
       rspan_for = x;
       cleared = fb > 0;
     }
-    if (mb > 0) hipLaunchKernelGGL(k_motion<false>, dim3(mb), dim3(kThreads), 0, stream, dp, x, f + 2 * hp.M, mJ, mctrl, 0, sq_part + dp.n_chunks);
+    if (mb > 0 && robust()) hipLaunchKernelGGL((k_motion<false, true>), dim3(mb), dim3(kThreads), 0, stream, dp, x, f + 2 * hp.M, mJ, mctrl, 0, sq_part + dp.n_chunks, loss);
+    else if (mb > 0) hipLaunchKernelGGL(k_motion<false>, dim3(mb), dim3(kThreads), 0, stream, dp, x, f + 2 * hp.M, mJ, mctrl, 0, sq_part + dp.n_chunks);
     if (host_sum) { sq_pend[set].slot = out - scal_out(); sq_pend[set].n = dp.n_chunks + mb; }      // added up by fetch()
     else if (dp.n_chunks + mb > 0) hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kThreads), 0, stream, dp.n_chunks + mb, sq_part, out);
     else MVUS_HIP(hipMemsetAsync(out, 0, sizeof(double), stream));
@@ -1248,6 +1259,41 @@ int mvus_ba_normal_equations(mvus_ba* h, double* g, double* JtJ_cam, double* ban
   });
 }
 
+int mvus_ba_set_loss(mvus_ba* h, int32_t loss, double f_scale) {
+  return guarded(h, [&] {
+    HipBackend& be = h->be;
+    if (loss < MVUS_LOSS_LINEAR || loss > MVUS_LOSS_ARCTAN) { be.err = "set_loss: unknown loss " + std::to_string(loss); return MVUS_E_INVALID; }
+    if (!std::isfinite(f_scale) || !(f_scale > 0)) { be.err = "set_loss: f_scale must be finite and positive"; return MVUS_E_INVALID; }
+    // what an LM solve left for its point is the cost and the normal equations of the OLD loss: dropped (f(x) is evaluated again, the same
+    // bits); a changed loss is another problem, so the damping starts where a fresh handle's does
+    be.carry = LmCarry{};
+    if (loss != be.loss.kind || f_scale != be.loss.fs) { be.lm_lambda = 0; be.lm_nu = 0; }
+    be.loss = LossSpec{loss, f_scale};
+    return MVUS_OK;
+  });
+}
+
+int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* weights_out) {
+  return guarded(h, [&] {
+    HipBackend& be = h->be;
+    if (!x || !cost_out) { be.err = "robust_cost: NULL argument"; return MVUS_E_INVALID; }
+    if (be.allreduce || be.tshard.on) { be.err = "robust_cost: not supported on a sharded handle"; return MVUS_E_UNSUPPORTED; }
+    be.upload(be.x_cur, x, be.hp.n);
+    be.residual_sq(be.x_cur, be.f_cur, be.scal_out() + 3);      // (slot 3: outside the LM driver's, inside the host-summed range)
+    double twice = 0;
+    be.fetch(be.scal_out() + 3, 1, &twice);
+    *cost_out = 0.5 * twice;
+    if (weights_out) {
+      PoolGuard<HipBackend> pool(be);
+      double* w = pool.get(be.hp.m);
+      if (be.hp.m > 0) hipLaunchKernelGGL(k_loss_weights, dim3((unsigned)((be.hp.m + kThreads - 1) / kThreads)), dim3(kThreads), 0, be.stream, (long long)be.hp.m, (const double*)be.f_cur, be.loss, w);
+      MVUS_HIP(hipGetLastError());
+      be.download(weights_out, w, be.hp.m);
+    }
+    return MVUS_OK;
+  });
+}
+
 int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
   return guarded(h, [&] {
     HipBackend& be = h->be;
@@ -1290,6 +1336,13 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
     if (so.jac_mode == MVUS_JAC_FD && (!be.has_pattern || be.fd_ngroups <= 0)) {
       be.err = "MVUS_JAC_FD: call mvus_ba_set_pattern(x0) and mvus_ba_set_fd_groups first";
       return MVUS_E_INVALID;
+    }
+    if (be.robust()) {               // what the loss does not reach refuses: it never silently solves the linear problem
+      const char* what = opts->solver != MVUS_SOLVER_LM_SCHUR ? "MVUS_SOLVER_TRF_LSMR"
+                         : so.jac_mode != MVUS_JAC_ANALYTIC   ? "a Jacobian mode other than MVUS_JAC_ANALYTIC"
+                         : (be.allreduce || be.tshard.on)     ? "a sharded handle (set_allreduce / set_rccl / set_time_shard)"
+                                                              : nullptr;
+      if (what) { be.err = std::string("a robust loss (mvus_ba_set_loss) is not supported with ") + what + ": MVUS_SOLVER_LM_SCHUR with MVUS_JAC_ANALYTIC on one rank only"; return MVUS_E_UNSUPPORTED; }
     }
     SolveResult sr;
     be.held_analytic_at_xcur = false;
@@ -1547,6 +1600,7 @@ int mvus_ba_time_kernel(mvus_ba* h, int32_t which, int32_t launches, double* avg
     auto launch = [&]() {
       switch (which) {
         case 0:
+          if (be.robust()) { be.residual_sq(be.x_cur, be.f_cur, be.scal_dev + 3); break; }      // (the cost evaluation of a robust LM trial: + motion rows and the final sum)
           if (be.hp.calib) hipLaunchKernelGGL((k_observations<true, false>), g, b, 0, be.stream, be.dp, be.cams, be.x_cur, be.f_cur, be.J, be.rspan, be.pat0, 0);
           else hipLaunchKernelGGL((k_observations<false, false>), g, b, 0, be.stream, be.dp, be.cams, be.x_cur, be.f_cur, be.J, be.rspan, be.pat0, 0);
           break;

@@ -122,9 +122,16 @@ MVUS_HD int win_pieces(int Wn) { const int a = 21 / Wn, b = 32 / (Wn + 3); retur
 constexpr __host__ __device__ int win_wave_doubles(int B) { return win_region_doubles(B) + 32; }   // staging / flush region + span masks
 constexpr __host__ __device__ int win_lds_doubles(int B) { return kWinWaves * win_wave_doubles(B) + kWinMaxJ * kWinSpl; }   // + the window's span records
 
-template <int B>
+// ROBUST (a loss other than linear in force on the handle, mvus_ba_set_loss): the two rows of a detection are scaled where they are
+// STAGED -- s_x Jx, s_x gu, rho'_x ex / s_x and the same for y (loss_scale_row), one lane per staged column between the staging and
+// the first reader -- so every product formed afterwards is that of the robust system with the same order of additions; the linear
+// instantiation is the kernel without a loss, instruction for instruction.
+template <int B, bool ROBUST = false, class... L>
 __global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_waves_per_eu(B == 9 ? MVUS_WIN_WAVES_PER_EU : 1, B == 9 ? MVUS_WIN_WAVES_PER_EU : 1)))
-void k_assemble_windows(DevProblem dp, NEView ne, WinView wv, const CamState* __restrict__ cams, const double* __restrict__ x) {
+void k_assemble_windows(DevProblem dp, NEView ne, WinView wv, const CamState* __restrict__ cams, const double* __restrict__ x,
+                        L... loss_v) {
+  static_assert(sizeof...(L) == (ROBUST ? 1 : 0), "the robust instantiation is launched with its LossSpec, the linear one without");
+  const LossSpec loss = loss_arg(loss_v...);
   constexpr bool CALIB = B == 18;
   using R = WinRows<B>;
   constexpr int NV = R::kRows;
@@ -215,7 +222,11 @@ void k_assemble_windows(DevProblem dp, NEView ne, WinView wv, const CamState* __
   auto fetch = [&](int pos, int p1) {
     Inputs in{0.0, 0.0, 0.0, 0.0, -1};
     if (pos < p1) {                                         // (five independent loads: nothing here waits for the span)
-      const long long i = pos;
+      int pi = pos;
+      // (the robust variant: the five addresses are formed here, from an index the optimiser cannot see through -- formed early, the span
+      // table's was kept across the evaluation in a register the kernel does not have, and spilled)
+      if constexpr (ROBUST) asm volatile("" : "+v"(pi));
+      const long long i = pi;
       in.g = wv.span[i];
       in.fr = dp.frame[i]; in.vr = dp.v_raw[i];
       in.p = CALIB ? dp.u_raw[i] : dp.u_obs[i];
@@ -298,6 +309,27 @@ void k_assemble_windows(DevProblem dp, NEView ne, WinView wv, const CamState* __
         }
       }
       win_wave_sync();
+      if constexpr (ROBUST) {
+        // the loss, where the rows are staged: lane = staged column (the columns in use are contiguous).  A pass of its own behind the
+        // evaluation -- inside it the scales' arithmetic met the evaluation's registers and spilled -- and a loop of two, not unrolled:
+        // the x row is finished before the y row's scale is computed
+        if (lane < __popcll(valid)) {
+          double* col = S + lane;
+#pragma unroll 1
+          for (int xy = 0; xy < 2; ++xy) {
+            double fr = col[(kFx + xy) * kWinStr];
+            const double sc = loss_scale_row(loss, fr);
+            double* g3 = col + (R::kGu + 3 * xy) * kWinStr;
+            double* jb = col + (R::kJx + B * xy) * kWinStr;
+#pragma unroll
+            for (int e = 0; e < 3; ++e) g3[e * kWinStr] *= sc;
+#pragma unroll
+            for (int k = 0; k < B; ++k) jb[k * kWinStr] *= sc;
+            col[(kFx + xy) * kWinStr] = fr;
+          }
+        }
+        win_wave_sync();
+      }
       // the masks of the four spans that reach this lane's control point (its piece of each): span pl + 3 - q touches it as ITS control point q
       unsigned long long mq[4];
 #pragma unroll

@@ -223,12 +223,16 @@ struct JStoreSink {
   __device__ __forceinline__ void y(int k, double v) { if (live) MVUS_JSTORE(&(Jy + (long long)k * stride)[lane], keep(k, v)); }
 };
 
-template <bool CALIB, bool JAC>
+// ROBUST (residual-only launches with sq_part, a loss other than linear in force): the chunk's partial is the sum of f_scale^2 rho(z)
+// instead of f^2 -- twice the robust cost, in the same layout and summation order; f itself stays the raw error_BA.
+template <bool CALIB, bool JAC, bool ROBUST = false, class... L>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JAC ? (CALIB ? MVUS_JAC_WAVES_CALIB : MVUS_JAC_WAVES) : 4, 8))) void k_observations(DevProblem dp, const CamState* __restrict__ cams,
                                                            const double* __restrict__ x, double* __restrict__ f,
                                                            double* __restrict__ J, int32_t* __restrict__ span,
                                                            const int32_t* __restrict__ pat0, int masked, double* __restrict__ sq_part = nullptr,
-                                                           double* __restrict__ clr = nullptr, long long clr_len = 0) {
+                                                           double* __restrict__ clr = nullptr, long long clr_len = 0, L... loss_v) {
+  static_assert(sizeof...(L) == (ROBUST ? 1 : 0), "the robust instantiation is launched with its LossSpec, the linear one without");
+  const LossSpec loss = loss_arg(loss_v...);
   constexpr int NS = 3 + (CALIB ? 15 : 6) + 12;
   // JAC: the grid is xcd_grid(n_chunks) workgroups and each XCD works on runs of consecutive chunks (xcd_tile): the kernel
   // is bound by its store stream, and an L2 that writes back runs of consecutive lines of each slot row reaches 12-14 %
@@ -264,7 +268,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(JAC ? 
         f[2 * a + (i - a)] = r.ex;
         f[2 * a + Mc + (i - a)] = r.ey;
         if (span != nullptr) span[i] = r.ctrl;           // (residual-only launches: the span table the fused assembly starts from)
-        sq = r.ex * r.ex + r.ey * r.ey;
+        if constexpr (ROBUST) sq = loss_rho(loss, r.ex) + loss_rho(loss, r.ey);
+        else sq = r.ex * r.ex + r.ey * r.ey;
       }
       sq = wave_sum(sq);
       if ((threadIdx.x & 63) == 0) sq_red[threadIdx.x >> 6] = sq;
@@ -305,9 +310,12 @@ __global__ __launch_bounds__(kThreads) void k_pattern(DevProblem dp, const CamSt
 }
 
 // Motion-regulariser rows (error_motion / motion_prior): one thread per sample.
-template <bool JAC>
+template <bool JAC, bool ROBUST = false, class... L>
 __global__ __launch_bounds__(kThreads) void k_motion(DevProblem dp, const double* __restrict__ x, double* __restrict__ fm,
-                                                     double* __restrict__ mJ, int32_t* __restrict__ mctrl, int masked, double* __restrict__ sq_part = nullptr) {
+                                                     double* __restrict__ mJ, int32_t* __restrict__ mctrl, int masked, double* __restrict__ sq_part = nullptr,
+                                                     L... loss_v) {
+  static_assert(sizeof...(L) == (ROBUST ? 1 : 0), "the robust instantiation is launched with its LossSpec, the linear one without");
+  const LossSpec loss = loss_arg(loss_v...);
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if constexpr (!JAC) {
     if (sq_part != nullptr) {                            // residual-only, with the workgroup's sum of squares (see k_observations)
@@ -318,7 +326,7 @@ __global__ __launch_bounds__(kThreads) void k_motion(DevProblem dp, const double
         if (key >= dp.mot_lo && key < dp.mot_hi) { double jrow[36]; int32_t cidx[3]; v = eval_motion_row<false>(dp.mv, x, j, false, jrow, cidx); }
         fm[j] = v;
       }
-      double sq = wave_sum(v * v);
+      double sq = wave_sum(ROBUST ? loss_rho(loss, v) : v * v);
       if ((threadIdx.x & 63) == 0) sq_red[threadIdx.x >> 6] = sq;
       __syncthreads();
       if (threadIdx.x == 0) {
@@ -735,6 +743,12 @@ __global__ void k_fill(long long len, double v, double* out, int tiles) {
   for (long long i = t * (long long)blockDim.x + threadIdx.x; i < len; i += (long long)tiles * blockDim.x) out[i] = v;
 }
 // deterministic two-stage dot product: per-workgroup partials, then one workgroup sums them
+// weights_out of mvus_ba_robust_cost: rho'((f_i / f_scale)^2) of every row
+__global__ __launch_bounds__(kThreads) void k_loss_weights(long long m, const double* __restrict__ f, LossSpec loss, double* __restrict__ w) {
+  const long long i = blockIdx.x * (long long)kThreads + threadIdx.x;
+  if (i < m) w[i] = loss_weight(loss, f[i]);
+}
+
 __global__ __launch_bounds__(kThreads) void k_dot_partial(long long len, const double* __restrict__ a, const double* __restrict__ b,
                                                           double* __restrict__ partials) {
   __shared__ double red[kThreads / 64];

@@ -672,4 +672,57 @@ MVUS_HD double fd_step(double x, double lb, double ub) {
   return h;
 }
 
+// Robust loss of scipy.optimize.least_squares(loss=, f_scale=) (scipy/optimize/_lsq/least_squares.py: soft_l1, huber, cauchy, arctan and
+// construct_loss_function; _lsq/common.py: scale_for_robust_loss_function), row by row: with z = (f / f_scale)^2
+//   cost          0.5 f_scale^2 sum rho(z)
+//   linearisation J_i <- s J_i, f_i <- rho' f_i / s,  s = sqrt(max(rho' + 2 rho'' z, EPS))
+// kind: MVUS_LOSS_* of include/mvus_ba.h (0 = linear: rho = z).  Uniform over a launch.
+struct LossSpec {
+  int kind;
+  double fs;
+};
+struct RowLoss {
+  double rho, d1, d2;    // rho(z), rho'(z), rho''(z)
+};
+// The kernels that have a ROBUST variant take the loss as a trailing parameter PACK: the linear instantiation is launched without it
+// and keeps the argument list -- and the kernel-argument segment -- it has always had
+MVUS_HD LossSpec loss_arg() { return LossSpec{0, 1.0}; }
+MVUS_HD LossSpec loss_arg(const LossSpec& l) { return l; }
+MVUS_HD RowLoss loss_terms(int kind, double z) {
+  RowLoss r{z, 1.0, 0.0};
+  if (kind == 1) {                    // soft_l1
+    const double t = 1.0 + z, q = sqrt(t);
+    r.rho = 2.0 * (q - 1.0); r.d1 = 1.0 / q; r.d2 = -0.5 / (t * q);
+  } else if (kind == 2) {             // huber
+    if (z > 1.0) { const double q = sqrt(z); r.rho = 2.0 * q - 1.0; r.d1 = 1.0 / q; r.d2 = -0.5 / (z * q); }
+  } else if (kind == 3) {             // cauchy
+    const double t = 1.0 + z;
+    r.rho = log1p(z); r.d1 = 1.0 / t; r.d2 = -1.0 / (t * t);
+  } else if (kind == 4) {             // arctan
+    const double t = 1.0 + z * z;
+    r.rho = atan(z); r.d1 = 1.0 / t; r.d2 = -2.0 * z / (t * t);
+  }
+  return r;
+}
+// f_scale^2 rho((f / f_scale)^2): the row's share of twice the cost
+MVUS_HD double loss_rho(const LossSpec& L, double f) {
+  const double u = f / L.fs;
+  return L.fs * L.fs * loss_terms(L.kind, u * u).rho;
+}
+// rho'((f / f_scale)^2): the weight of the row in the gradient
+MVUS_HD double loss_weight(const LossSpec& L, double f) {
+  const double u = f / L.fs;
+  return loss_terms(L.kind, u * u).d1;
+}
+// the row's scale s of the Jacobian; f becomes the residual of the scaled row, rho' f / s
+MVUS_HD double loss_scale_row(const LossSpec& L, double& f) {
+  const double u = f / L.fs, z = u * u;
+  const RowLoss r = loss_terms(L.kind, z);
+  const double eps = 2.220446049250313e-16;
+  const double js = r.d1 + 2.0 * r.d2 * z;
+  const double s = sqrt(js < eps ? eps : js);
+  f *= r.d1 / s;
+  return s;
+}
+
 }  // namespace mvus

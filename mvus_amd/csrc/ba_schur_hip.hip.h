@@ -88,10 +88,14 @@ struct LdsRowSink {          // eval_observation_to sink: slot k of the x / y ro
   __device__ __forceinline__ void x(int k, double v) { col[k * kGaStride] = v; }
   __device__ __forceinline__ void y(int k, double v) { col[(ns + k) * kGaStride] = v; }
 };
-template <int NS, bool FUSED>
+// ROBUST (a loss other than linear in force): every staged row is scaled as it is staged -- s J and rho' f / s of loss_scale_row --
+// so the sums below are those of the robust system; f in memory stays the raw error_BA.
+template <int NS, bool FUSED, bool ROBUST = false, class... L>
 __global__ __launch_bounds__(kGaThreads) void k_assemble_spans(DevProblem dp, const double* __restrict__ J, const int32_t* __restrict__ span,
                                                              const double* __restrict__ f, NEView ne, const CamState* __restrict__ cams,
-                                                             const double* __restrict__ x) {
+                                                             const double* __restrict__ x, L... loss_v) {
+  static_assert(sizeof...(L) == (ROBUST ? 1 : 0), "the robust instantiation is launched with its LossSpec, the linear one without");
+  const LossSpec loss = loss_arg(loss_v...);
   constexpr int B = NS - 12;
   constexpr int kJs = (2 * NS + 2) * kGaStride;
   constexpr int kEp = 4 * 3 * B, kGp = 12, kCp = 10 * 9;        // partial block sizes per range: cross, gradient, band
@@ -135,7 +139,15 @@ __global__ __launch_bounds__(kGaThreads) void k_assemble_spans(DevProblem dp, co
       const ObsResult r = eval_observation_to<CALIB, true>(cam, dp.sp, x, dp.undist != 0, dp.rs_free != 0, dp.sync_free != 0,
                                                            dp.frame[i], ur, dp.v_raw[i], uo, vo, sink);
       g = r.ctrl;
-      if (g >= 0) { Js[(2 * NS) * kGaStride + t] = r.ex; Js[(2 * NS + 1) * kGaStride + t] = r.ey; }
+      if (g >= 0) {
+        double fx = r.ex, fy = r.ey;
+        if constexpr (ROBUST) {
+          const double sx = loss_scale_row(loss, fx), sy = loss_scale_row(loss, fy);
+#pragma unroll
+          for (int k = 0; k < NS; ++k) { Js[k * kGaStride + t] *= sx; Js[(NS + k) * kGaStride + t] *= sy; }
+        }
+        Js[(2 * NS) * kGaStride + t] = fx; Js[(2 * NS + 1) * kGaStride + t] = fy;
+      }
     }
     kt = g >= 0 ? g : 0x7fffffff;
     if (tid < kGaObs) key[tid] = kt;
@@ -152,6 +164,12 @@ __global__ __launch_bounds__(kGaThreads) void k_assemble_spans(DevProblem dp, co
       if (g >= 0) {
         if (r < 2 * NS) v = J[j_chunk_offset<NS>(chunk) + r * kThreads + half * kGaObs + t];
         else v = f[2 * a0 + (r - 2 * NS) * Mc + (i0 + t - a0)];
+        if constexpr (ROBUST) {                          // the row's own residual decides its scale: x rows r < NS and 2 NS, y rows the others
+          const bool yrow = r < 2 * NS ? r >= NS : r == 2 * NS + 1;
+          double fr = f[2 * a0 + (yrow ? Mc : 0) + (i0 + t - a0)];
+          const double sc = loss_scale_row(loss, fr);
+          v = r < 2 * NS ? v * sc : fr;
+        }
       }
       Js[r * kGaStride + t] = v;
     }
@@ -492,8 +510,12 @@ __global__ __launch_bounds__(1024) void k_cam_block_reduce(DevProblem dp, NEView
 // 256 consecutive rows (= consecutive sample times) per workgroup; each row is first compacted to the <= 6
 // distinct control points it touches, then accumulated into an LDS window like the detection rows.
 constexpr int kMotW = 6;
+// (ROBUST, here and in the two row-ordered kernels below: the row's coefficients times s, its residual rho' f / s -- loss_scale_row)
+template <bool ROBUST = false, class... L>
 __global__ __launch_bounds__(kThreads) void k_assemble_motion(DevProblem dp, const double* __restrict__ mJ, const int32_t* __restrict__ mctrl,
-                                                              const double* __restrict__ fm, NEView ne) {
+                                                              const double* __restrict__ fm, NEView ne, L... loss_v) {
+  static_assert(sizeof...(L) == (ROBUST ? 1 : 0), "the robust instantiation is launched with its LossSpec, the linear one without");
+  const LossSpec loss = loss_arg(loss_v...);
   __shared__ double Cw[kNWin * kMotW * 9];
   __shared__ double gsw[kNWin * 3];
   __shared__ int gmin_s[kThreads / 64];
@@ -540,7 +562,12 @@ __global__ __launch_bounds__(kThreads) void k_assemble_motion(DevProblem dp, con
   for (int w = 1; w < kThreads / 64; ++w) g0 = min(g0, gmin_s[w]);
   if (g0 == 0x7fffffff) return;
   if (live) {
-    const double fj = fm[j];
+    double fj = fm[j];
+    if constexpr (ROBUST) {
+      const double sc = loss_scale_row(loss, fj);
+#pragma unroll
+      for (int e = 0; e < kMotW * 3; ++e) rv[e] *= sc;
+    }
     const int l = lo - g0;
     const bool inwin = l + kMotW <= kNWin;
 #pragma unroll
@@ -583,8 +610,11 @@ __global__ __launch_bounds__(kThreads) void k_assemble_motion(DevProblem dp, con
 // go to LDS; then lane = ENTRY (gradient coordinate, or band entry (w, d, d2)) adds the rows in row order.  One order of additions
 // per entry, no atomics.  Rows k_assemble_motion skips (outside the slice, wider than kMotW control points) are zeros here.
 constexpr int kDetMotW = 6;                              // >= ne.W (the band solver supports at most six 3x3 blocks)
+template <bool ROBUST = false, class... L>
 __global__ __launch_bounds__(kThreads) void k_det_motion(DevProblem dp, const double* __restrict__ mJ, const int32_t* __restrict__ mctrl,
-                                                         const double* __restrict__ fm, NEView ne) {
+                                                         const double* __restrict__ fm, NEView ne, L... loss_v) {
+  static_assert(sizeof...(L) == (ROBUST ? 1 : 0), "the robust instantiation is launched with its LossSpec, the linear one without");
+  const LossSpec loss = loss_arg(loss_v...);
   constexpr int kWaves = kThreads / 64, kRv = kDetMotW * 3 + 1;       // per row: W x 3 coefficients + the residual
   __shared__ double rv[kWaves][64][kRv + 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -630,7 +660,13 @@ __global__ __launch_bounds__(kThreads) void k_det_motion(DevProblem dp, const do
             }
           }
         }
-        r[kDetMotW * 3] = fm[j];
+        double fj = fm[j];
+        if constexpr (ROBUST) {
+          const double sc = loss_scale_row(loss, fj);
+#pragma unroll
+          for (int e = 0; e < kDetMotW * 3; ++e) r[e] *= sc;
+        }
+        r[kDetMotW * 3] = fj;
       }
     }
 #pragma unroll
@@ -656,8 +692,11 @@ __global__ __launch_bounds__(kThreads) void k_det_motion(DevProblem dp, const do
 // a row then span more than three knot spans; the band has W <= kWideW blocks per row): one wavefront per control point, the rows'
 // coefficients built in LDS by the row's own lane, every lane adds up to three entries of the control point's band row.
 constexpr int kWideW = 16;
+template <bool ROBUST = false, class... L>
 __global__ __launch_bounds__(64) void k_det_motion_wide(DevProblem dp, const double* __restrict__ mJ, const int32_t* __restrict__ mctrl,
-                                                        const double* __restrict__ fm, NEView ne) {
+                                                        const double* __restrict__ fm, NEView ne, L... loss_v) {
+  static_assert(sizeof...(L) == (ROBUST ? 1 : 0), "the robust instantiation is launched with its LossSpec, the linear one without");
+  const LossSpec loss = loss_arg(loss_v...);
   constexpr int kRv = kWideW * 3 + 1;                      // per row: W x 3 coefficients + the residual
   __shared__ double rv[64][kRv + 1];
   const int lane = threadIdx.x, g = blockIdx.x;
@@ -690,7 +729,12 @@ __global__ __launch_bounds__(64) void k_det_motion_wide(DevProblem dp, const dou
             for (int dd = 0; dd < 3; ++dd) rv[lane][3 * a + dd] += mJ[(long long)(12 * k + 3 * q + dd) * dp.T + j];
           }
         }
-        rv[lane][kWideW * 3] = fm[j];
+        double fj = fm[j];
+        if constexpr (ROBUST) {
+          const double sc = loss_scale_row(loss, fj);
+          for (int e = 0; e < kWideW * 3; ++e) rv[lane][e] *= sc;
+        }
+        rv[lane][kWideW * 3] = fj;
       }
     }
     lds_wave_sync();
@@ -2903,6 +2947,15 @@ struct HipSchur {
     if (hp.calib) MVUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_windows<18>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_lds));
     else MVUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_windows<9>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_lds));
   }
+  // the robust instantiation's dynamic LDS limit: set when a loss is first used on the handle (a handle without a loss does at
+  // construction exactly what it always did)
+  bool win_robust_ready = false;
+  void win_robust_prepare() {
+    if (win_robust_ready) return;
+    if (be.hp.calib) MVUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_windows<18, true, LossSpec>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_lds));
+    else MVUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_windows<9, true, LossSpec>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_lds));
+    win_robust_ready = true;
+  }
   ~HipSchur() {
     for (double* p : {wv.band_part, Rloc, CGK, cutbuf, cutws, Dl, NEset[0], NEset[1], Lb, Z, G, G0, S, S2, Linv, rhs, pc, DG, px, pv.VW, sepbuf, pv.U2, pv.Ha, pv.Hc, wv.Apart, rcs.Simg, rcs.Tsc, rcs.x}) if (p) be.release(p);
     if (win_tables) (void)hipFree(win_tables);
@@ -2959,14 +3012,22 @@ struct HipSchur {
   void motion_rows(const double* f_dev) {
     // (one rank: the row-ordered kernel in both modes -- 22 us against 26 for the LDS-window one at configs[1], and one source of
     // run-to-run differences less; a time shard keeps k_assemble_motion, which also reports rows that leave the slice)
-    if (be.hp.T > 0 && wide) {
-      hipLaunchKernelGGL(k_det_motion_wide, dim3((unsigned)ne.N), dim3(64), 0, be.stream, be.dp, be.mJ, be.mctrl, f_dev + 2 * be.hp.M, ne);
-    } else if (be.hp.T > 0 && !shard && ne.W <= kDetMotW) {
-      hipLaunchKernelGGL(k_det_motion, dim3((unsigned)((ne.N + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, be.stream, be.dp, be.mJ, be.mctrl,
-                         f_dev + 2 * be.hp.M, ne);
-    } else if (be.hp.T > 0)
-      hipLaunchKernelGGL(k_assemble_motion, dim3((be.hp.T + kThreads - 1) / kThreads), dim3(kThreads), 0, be.stream, be.dp, be.mJ, be.mctrl,
-                         f_dev + 2 * be.hp.M, ne);
+    if (be.hp.T <= 0) return;
+    const double* fm = f_dev + 2 * be.hp.M;
+    const LossSpec loss = be.loss;
+    if (wide) {
+      const dim3 g((unsigned)ne.N), b(64);
+      if (be.robust()) hipLaunchKernelGGL(k_det_motion_wide<true>, g, b, 0, be.stream, be.dp, be.mJ, be.mctrl, fm, ne, loss);
+      else hipLaunchKernelGGL(k_det_motion_wide<false>, g, b, 0, be.stream, be.dp, be.mJ, be.mctrl, fm, ne);
+    } else if (!shard && ne.W <= kDetMotW) {
+      const dim3 g((unsigned)((ne.N + kThreads / 64 - 1) / (kThreads / 64))), b(kThreads);
+      if (be.robust()) hipLaunchKernelGGL(k_det_motion<true>, g, b, 0, be.stream, be.dp, be.mJ, be.mctrl, fm, ne, loss);
+      else hipLaunchKernelGGL(k_det_motion<false>, g, b, 0, be.stream, be.dp, be.mJ, be.mctrl, fm, ne);
+    } else {
+      const dim3 g((be.hp.T + kThreads - 1) / kThreads), b(kThreads);
+      if (be.robust()) hipLaunchKernelGGL(k_assemble_motion<true>, g, b, 0, be.stream, be.dp, be.mJ, be.mctrl, fm, ne, loss);
+      else hipLaunchKernelGGL(k_assemble_motion<false>, g, b, 0, be.stream, be.dp, be.mJ, be.mctrl, fm, ne);
+    }
   }
   void assemble_local(const double* f_dev, const double* x_fused = nullptr, const int32_t* span_held = nullptr) {
     if (x_fused && use_win) {
@@ -2984,13 +3045,16 @@ struct HipSchur {
         wv.span = be.rspan;
       }
       be.ensure_cams(x_fused);
+      if (be.robust()) win_robust_prepare();
       if (be.hp.calib) {
         const unsigned sumg = (unsigned)be.hp.C + (wv.G > 1 ? (unsigned)(((long long)ne.N * (3 + ne.W * 9) + 1023) / 1024) : 0u);
-        hipLaunchKernelGGL(k_assemble_windows<18>, dim3(wv.nwin * wv.G), dim3(kWinThreads), win_lds, be.stream, be.dp, ne, wv, be.cams, x_fused);
+        if (be.robust()) hipLaunchKernelGGL((k_assemble_windows<18, true>), dim3(wv.nwin * wv.G), dim3(kWinThreads), win_lds, be.stream, be.dp, ne, wv, be.cams, x_fused, be.loss);
+        else hipLaunchKernelGGL((k_assemble_windows<18, false>), dim3(wv.nwin * wv.G), dim3(kWinThreads), win_lds, be.stream, be.dp, ne, wv, be.cams, x_fused);
         hipLaunchKernelGGL(k_cam_block_sum<18>, dim3(sumg), dim3(1024), 0, be.stream, be.hp.C, wv.nwin, wv.Apart, ne, wv.G, (const double*)wv.band_part, zr, zn);
       } else {
         const unsigned sumg = (unsigned)be.hp.C + (wv.G > 1 ? (unsigned)(((long long)ne.N * (3 + ne.W * 9) + 1023) / 1024) : 0u);
-        hipLaunchKernelGGL(k_assemble_windows<9>, dim3(wv.nwin * wv.G), dim3(kWinThreads), win_lds, be.stream, be.dp, ne, wv, be.cams, x_fused);
+        if (be.robust()) hipLaunchKernelGGL((k_assemble_windows<9, true>), dim3(wv.nwin * wv.G), dim3(kWinThreads), win_lds, be.stream, be.dp, ne, wv, be.cams, x_fused, be.loss);
+        else hipLaunchKernelGGL((k_assemble_windows<9, false>), dim3(wv.nwin * wv.G), dim3(kWinThreads), win_lds, be.stream, be.dp, ne, wv, be.cams, x_fused);
         hipLaunchKernelGGL(k_cam_block_sum<9>, dim3(sumg), dim3(1024), 0, be.stream, be.hp.C, wv.nwin, wv.Apart, ne, wv.G, (const double*)wv.band_part, zr, zn);
       }
       motion_rows(f_dev);
@@ -3005,11 +3069,24 @@ struct HipSchur {
       const dim3 g(kGaParts * nc), b(kGaThreads);
       if (x_fused) {
         be.ensure_cams(x_fused);
-        if (be.hp.calib) hipLaunchKernelGGL((k_assemble_spans<30, true>), g, b, 0, be.stream, be.dp, (const double*)nullptr, (const int32_t*)nullptr, f_dev, ne, be.cams, x_fused);
-        else hipLaunchKernelGGL((k_assemble_spans<21, true>), g, b, 0, be.stream, be.dp, (const double*)nullptr, (const int32_t*)nullptr, f_dev, ne, be.cams, x_fused);
+        const double* nj = nullptr;
+        const int32_t* ns = nullptr;
+        if (be.robust()) {
+          if (be.hp.calib) hipLaunchKernelGGL((k_assemble_spans<30, true, true>), g, b, 0, be.stream, be.dp, nj, ns, f_dev, ne, be.cams, x_fused, be.loss);
+          else hipLaunchKernelGGL((k_assemble_spans<21, true, true>), g, b, 0, be.stream, be.dp, nj, ns, f_dev, ne, be.cams, x_fused, be.loss);
+        } else {
+          if (be.hp.calib) hipLaunchKernelGGL((k_assemble_spans<30, true, false>), g, b, 0, be.stream, be.dp, nj, ns, f_dev, ne, be.cams, x_fused);
+          else hipLaunchKernelGGL((k_assemble_spans<21, true, false>), g, b, 0, be.stream, be.dp, nj, ns, f_dev, ne, be.cams, x_fused);
+        }
       } else {
-        if (be.hp.calib) hipLaunchKernelGGL((k_assemble_spans<30, false>), g, b, 0, be.stream, be.dp, be.J, be.span, f_dev, ne, be.cams, (const double*)nullptr);
-        else hipLaunchKernelGGL((k_assemble_spans<21, false>), g, b, 0, be.stream, be.dp, be.J, be.span, f_dev, ne, be.cams, (const double*)nullptr);
+        const double* nx = nullptr;
+        if (be.robust()) {
+          if (be.hp.calib) hipLaunchKernelGGL((k_assemble_spans<30, false, true>), g, b, 0, be.stream, be.dp, be.J, be.span, f_dev, ne, be.cams, nx, be.loss);
+          else hipLaunchKernelGGL((k_assemble_spans<21, false, true>), g, b, 0, be.stream, be.dp, be.J, be.span, f_dev, ne, be.cams, nx, be.loss);
+        } else {
+          if (be.hp.calib) hipLaunchKernelGGL((k_assemble_spans<30, false, false>), g, b, 0, be.stream, be.dp, be.J, be.span, f_dev, ne, be.cams, nx);
+          else hipLaunchKernelGGL((k_assemble_spans<21, false, false>), g, b, 0, be.stream, be.dp, be.J, be.span, f_dev, ne, be.cams, nx);
+        }
       }
     }
     if (be.dp.n_chunks > 0) {

@@ -29,6 +29,10 @@ Extra ``settings`` keys (all optional; a reference ``config.json`` has none of t
 ``ba_lm_wide_band`` with 'lm': what to do when the motion rows reach over more than six control points (knots less than a frame
                apart, i.e. more control points than detections): 'trf' (default) solves THAT problem with TRF + LSMR on the analytic
                Jacobian and says so, 'lm' keeps LM + Schur (general band solver, damping floor 0.3).
+``ba_loss``, ``ba_f_scale`` with 'lm': the ``loss`` ('linear' DEFAULT, 'soft_l1', 'huber', 'cauchy', 'arctan') and ``f_scale`` (default 1.0,
+               pixels) arguments of scipy's least_squares, which the reference never passes: gross outliers stop pulling on the first
+               BA, the one that runs before ``remove_outliers`` can cut them.  Not with 'trf' (ValueError), and a problem the
+               wide-band policy above would hand to TRF raises instead of dropping the loss.
 ``ba_deterministic`` accepted and ignored: the 'lm' solver's normal equations are assembled without floating-point atomics
                (one writer, one order of additions per entry) -- the same bits on every run by construction.
 ``opt_sync`` (reference key: False freezes alpha/beta), ``device``.
@@ -431,7 +435,10 @@ class Scene:
         print('Doing BA with {} cameras...\n'.format(numCam))
         st = self.settings
         solver, jac_mode = self.ba_mode()
+        loss, f_scale = self.ba_loss()
         h = self._resident_handle(prob, cams)      # stays resident for remove_outliers and the next BA
+        if h.loss != (loss, f_scale):              # (a handle that has the loss already keeps what its last solve carried over)
+            h.set_loss(loss, f_scale)
         opts = _ba._lib.default_opts(solver, jac_mode, max_iter)
         opts.lm_lambda_min = float(st.get('ba_lambda_min', opts.lm_lambda_min))
         opts.lm_trust_radius = float(st.get('ba_trust_radius', opts.lm_trust_radius))
@@ -446,6 +453,11 @@ class Scene:
             res = h.solve(model, opts=opts, ties=st.get('ba_pattern_ties', 'numpy'), matrix=jac_sparsity)
             res.solver_used = 'lm' if solver == _ba.SOLVER_LM_SCHUR else 'trf'
         except _ba.UnsupportedBySolver as e:
+            if loss != _ba.LOSS_LINEAR:
+                # the other solver has no robust loss: handing the problem over would silently solve the linear one
+                raise _ba.UnsupportedBySolver("settings['ba_loss'] = %r needs the LM solver, which does not take this problem (%s); the fallback "
+                                              "to ba_solver=trf would drop the loss -- set ba_lm_wide_band: 'lm' or ba_loss: 'linear'"
+                                              % (st.get('ba_loss'), e)) from e
             # LM + Schur keeps the spline block as a band of at most sixteen 3x3 blocks (MVUS_E_UNSUPPORTED beyond; FITPACK knots far
             # below one frame apart make the motion rows reach further).  The other GPU solver has no such limit: same analytic
             # Jacobian, TRF + LSMR instead of the normal equations.  Said aloud and recorded in the result, not silently.
@@ -483,7 +495,28 @@ class Scene:
         jac = st.get('ba_jacobian', default_jac)
         if jac not in modes:
             raise ValueError("settings['ba_jacobian'] must be one of %s, not %r" % (sorted(modes), jac))
+        self.ba_loss()                       # (validated with the rest: a bad ba_loss / ba_f_scale raises before any GPU call)
         return solver, modes[jac]
+
+    def ba_loss(self):
+        """(MVUS_LOSS_* code, f_scale) of settings['ba_loss'] / settings['ba_f_scale']: the ``loss`` and ``f_scale`` arguments of
+        scipy's least_squares, which the reference never passes ('linear', 1.0 -- also the defaults here).  A loss other than
+        'linear' needs ``ba_solver: 'lm'`` with the analytic Jacobian."""
+        from .. import ba as _ba
+        st = self.settings if isinstance(self.settings, dict) else {}
+        name = st.get('ba_loss', 'linear')
+        if not isinstance(name, str) or name not in _ba.LOSS_NAMES:
+            raise ValueError("settings['ba_loss'] must be one of %s, not %r" % (sorted(_ba.LOSS_NAMES), name))
+        f_scale = st.get('ba_f_scale', 1.0)
+        if isinstance(f_scale, bool) or not isinstance(f_scale, (int, float, np.integer, np.floating)) or not np.isfinite(f_scale) or not f_scale > 0:
+            raise ValueError("settings['ba_f_scale'] must be a finite positive number, not %r" % (f_scale,))
+        if name != 'linear':
+            if st.get('ba_solver', 'trf') != 'lm':
+                raise ValueError("settings['ba_loss'] = %r needs settings['ba_solver'] = 'lm' (the TRF + LSMR solver has no robust loss), not %r"
+                                 % (name, st.get('ba_solver', 'trf')))
+            if st.get('ba_jacobian', 'analytic') != 'analytic':
+                raise ValueError("settings['ba_loss'] = %r needs settings['ba_jacobian'] = 'analytic', not %r" % (name, st.get('ba_jacobian')))
+        return _ba.LOSS_NAMES[name], float(f_scale)
 
     def remove_outliers(self, cams, thres=30, verbose=False):
         """Drop detections whose reprojection error is >= thres (common.py:700-717); the mask is computed by
