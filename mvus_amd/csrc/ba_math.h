@@ -51,6 +51,7 @@ struct CamState {
 };
 
 // cv2.Rodrigues vector->matrix plus the matrix W used for the rotation-vector derivative.
+constexpr double kRodriguesSeries = 1e-2;   // |rvec| below which W comes from its power series
 MVUS_HD void rodrigues(const double r[3], double R[9], double W[9]) {
   const double th2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
   const double th = sqrt(th2);
@@ -63,9 +64,23 @@ MVUS_HD void rodrigues(const double r[3], double R[9], double W[9]) {
   R[0] = c + c1 * kx * kx;      R[1] = c1 * kx * ky - s * kz; R[2] = c1 * kx * kz + s * ky;
   R[3] = c1 * ky * kx + s * kz; R[4] = c + c1 * ky * ky;      R[5] = c1 * ky * kz - s * kx;
   R[6] = c1 * kz * kx - s * ky; R[7] = c1 * kz * ky + s * kx; R[8] = c + c1 * kz * kz;
+  const double vx[9] = {0.0, -r[2], r[1], r[2], 0.0, -r[0], -r[1], r[0], 0.0};
+  if (th < kRodriguesSeries) {
+    // W = R A = I + a [v]x + b [v]x^2,  a = (1 - cos th) / th^2,  b = (th - sin th) / th^3,  [v]x^2 = v v^T - th^2 I.  The closed form
+    // below divides differences of order th^2 (R^T - I times [v]x against v v^T) by th^2 and loses half the digits around th = 1e-8
+    // (4.9e-9 on W, which is perfectly conditioned there); the series, cut after th^6, is exact to the last bit below the seam, where the
+    // closed form is still good to ~1e-14 (tests/test_jacobian_exact_host.py sweeps the seam).
+    const double a = 0.5 - th2 * (1.0 / 24.0 - th2 * (1.0 / 720.0 - th2 * (1.0 / 40320.0)));
+    const double b = 1.0 / 6.0 - th2 * (1.0 / 120.0 - th2 * (1.0 / 5040.0 - th2 * (1.0 / 362880.0)));
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        const double id = (i == j) ? 1.0 : 0.0;
+        W[3 * i + j] = id + a * vx[3 * i + j] + b * (r[i] * r[j] - th2 * id);
+      }
+    return;
+  }
   // A = (v v^T + (R^T - I) [v]x) / |v|^2 ;  W = R A
   double Rt_I[9] = {R[0] - 1.0, R[3], R[6], R[1], R[4] - 1.0, R[7], R[2], R[5], R[8] - 1.0};
-  const double vx[9] = {0.0, -r[2], r[1], r[2], 0.0, -r[0], -r[1], r[0], 0.0};
   double A[9];
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) {
