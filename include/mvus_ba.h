@@ -146,8 +146,9 @@ void mvus_default_opts(mvus_solve_opts* opts);
 /* Layout check for bindings in other languages (ctypes / cgo / JNI stubs that restate the structs): writes sizeof(mvus_solve_opts),
  * sizeof(mvus_result), sizeof(mvus_problem) as this library was compiled (any pointer may be NULL) and returns MVUS_ABI_VERSION.  A
  * binding asserts these against its own struct definitions at load time -- mvus_solve_opts has grown over the rounds (lm_lambda_min,
- * lm_trust_radius) and a stale stub would otherwise hand the library a short buffer.  The version is raised whenever a struct or a
- * prototype of this header changes.  Stateless, no device is touched.  No reference counterpart (the reference has no FFI). */
+ * lm_trust_radius) and a stale stub would otherwise hand the library a short buffer.  The version is raised whenever a struct or an
+ * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen) does not raise
+ * it -- a binding that needs one finds it missing at load time.  Stateless, no device is touched.  No reference counterpart (the reference has no FFI). */
 #define MVUS_ABI_VERSION 8
 int32_t mvus_abi_sizes(int32_t* solve_opts_size, int32_t* result_size, int32_t* problem_size);
 
@@ -263,6 +264,25 @@ int mvus_ba_set_loss(mvus_ba* h, int32_t loss, double f_scale);
 /* 0.5 f_scale^2 sum rho((f_i / f_scale)^2) at x under the loss in force; weights_out[m] (may be NULL) = rho'(z_i), the weight each row
  * has in the gradient (1 = inlier, -> 0 = ignored), in the row order of f.  One rank only. */
 int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* weights_out);
+
+/* Hold chosen camera-side unknowns constant: frozen[k] = 1 keeps x[k] where it is, k over the head of x in its own order -- alpha(C),
+ * beta(C), rs(C), then the P parameters of every camera -- so count must be C * (3 + P); control points are not freezable.  frozen == NULL
+ * or count == 0 clears the mask, and a mask of zeros is no mask.  The reference can only switch whole groups off for every camera
+ * (opt_sync, the `rs` argument, opt_calib: common.py:512-518, 621); this is the per-parameter form: a hardware-synchronised pair (alpha, beta),
+ * a surveyed camera (pose), trusted intrinsics beside cameras that run opt_calib, or the gauge -- the first camera's pose and one translation
+ * component of the second take the seven degrees of freedom of the similarity away (Scene settings ba_gauge / ba_freeze).
+ * State of the handle, as the loss is: in force for every later mvus_ba_solve / mvus_ba_normal_equations / mvus_ba_lm_step until set again, kept
+ * over mvus_ba_remove_outliers; everything about error_BA itself (residual, mvus_ba_residual_jacobian, J v, J^T u, motion rows, outlier masks)
+ * stays raw.  With a mask the frozen columns of J are zero: in the normal equations g[k] = 0 and row and column k of H are zero except
+ * H[k][k] = 1 (so D[k] = 1 and lambda = 0 stays solvable), the step has p[k] = 0 and x[k] comes back from a solve with the bits it went in
+ * with -- both solvers, every Jacobian mode; under rs_bounds a held rs has no box in either solver (on a bound or outside [0, 1] it stays as given).  Setting or clearing drops what an earlier LM solve
+ * carried over (cost, normal equations, the speculative linearisation) and, when the mask changes, the damping history: after clearing, a
+ * solve is a fresh handle's bit for bit.  A handle without a mask runs exactly the kernels it ran before this entry point existed.
+ * MVUS_E_INVALID: count is neither 0 nor C * (3 + P), a value other than 0 or 1.  MVUS_E_UNSUPPORTED ("sharded" in the message): a non-empty
+ * mask on a sharded handle (set_allreduce / set_rccl / set_time_shard), here or -- when the route is installed afterwards -- from the calls
+ * above: never solved unmasked.  mvus_ba_num_frozen: the number of held unknowns (0 = no mask). */
+int mvus_ba_set_frozen(mvus_ba* h, const uint8_t* frozen, int64_t count);
+int64_t mvus_ba_num_frozen(const mvus_ba* h);
 
 /* The least_squares call of Scene.BA (common.py:670) -- x is read and overwritten with res.x.
  * lb/ub come from opts of the problem (rs_bounds).  f_out[m] may be NULL.  x, res and f_out are complete on return.  MVUS_SOLVER_LM_SCHUR

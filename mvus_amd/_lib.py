@@ -84,6 +84,8 @@ API = [
     ('mvus_ba_normal_equations', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
     ('mvus_ba_lm_step', ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p]),
     ('mvus_ba_set_loss', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
+    ('mvus_ba_set_frozen', ctypes.c_int, [ctypes.c_void_p, c_uint8_p, ctypes.c_int64]),
+    ('mvus_ba_num_frozen', ctypes.c_int64, [ctypes.c_void_p]),
     ('mvus_ba_robust_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
     ('mvus_ba_solve', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.POINTER(MvusSolveOpts), ctypes.POINTER(MvusResult), c_double_p]),
     ('mvus_ba_outlier_mask', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_uint8_p]),

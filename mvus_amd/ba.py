@@ -66,6 +66,7 @@ class BAHandle:
         self.M = prob.M
         self._cb = None
         self.loss = (LOSS_LINEAR, 1.0)     # (code, f_scale) in force: set_loss
+        self._frozen = None                # mask in force: set_frozen
 
     def close(self):
         if getattr(self, 'h', None):
@@ -230,6 +231,34 @@ class BAHandle:
         code = loss_code(loss)
         self._check(self.lib.mvus_ba_set_loss(self.h, code, float(f_scale)), 'mvus_ba_set_loss')
         self.loss = (code, float(f_scale))
+
+    def set_frozen(self, mask):
+        """Hold camera-side unknowns constant (mvus_ba_set_frozen): ``mask[k]`` true keeps ``x[k]`` where it is, k over the head of x in
+        pack_x order -- alpha(C), beta(C), rs(C), then P parameters per camera -- so ``mask`` has C * (3 + P) entries.  ``None`` (or an
+        empty mask) clears it.  In force for every later solve / normal_equations / lm_step on the handle, kept over remove_outliers;
+        residual, residual_jacobian, jv, jtu and the outlier masks stay those of error_BA."""
+        if mask is None or np.size(mask) == 0:
+            self._check(self.lib.mvus_ba_set_frozen(self.h, None, 0), 'mvus_ba_set_frozen')
+            self._frozen = None
+            return
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ and m.dtype != np.uint8:
+            if not np.all((m == 0) | (m == 1)):
+                raise ValueError('set_frozen: the mask holds values other than 0 and 1')
+        m = np.ascontiguousarray(m, dtype=np.uint8).ravel()
+        self._check(self.lib.mvus_ba_set_frozen(self.h, m.ctypes.data_as(_lib.c_uint8_p), m.size), 'mvus_ba_set_frozen')
+        self._frozen = m.astype(bool) if m.any() else None
+
+    @property
+    def frozen(self):
+        """The mask in force (bool[C * (3 + P)], a copy), or None without one."""
+        if int(self.lib.mvus_ba_num_frozen(self.h)) == 0:
+            return None
+        return self._frozen.copy()
+
+    @property
+    def num_frozen(self):
+        return int(self.lib.mvus_ba_num_frozen(self.h))
 
     def robust_cost(self, x, weights=False):
         """0.5 f_scale^2 sum rho((f_i / f_scale)^2) at x under the loss in force; with ``weights`` also rho' of every row of f

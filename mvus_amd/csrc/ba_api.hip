@@ -505,6 +505,39 @@ struct HipBackend {
   // the rows as they read them; f in memory is the raw error_BA throughout.  (Sharded handles refuse a loss: mvus_ba_solve.)
   LossSpec loss{0, 1.0};
   bool robust() const { return loss.kind != 0; }
+  // Camera-side unknowns held constant (mvus_ba_set_frozen), state of the handle like the loss.  frozen_mask: the caller's mask over the
+  // head of x in pack_x order (empty = none); on the device the same set twice, in the solvers' internal order e = c * B + slot: the list
+  // of frozen entries (k_freeze_ne, LM + Schur: one workgroup each) and a byte per entry (k_freeze_jacobian, TRF + LSMR).  An all-zero mask
+  // is no mask: frozen_count = 0 and no kernel, argument or branch on the device differs from a handle that never had one.
+  std::vector<uint8_t> frozen_mask;
+  int32_t* frozen_idx = nullptr;
+  uint8_t* frozen_slot = nullptr;
+  int frozen_count = 0;
+  bool freeze_stored_jacobian = false;      // inside mvus_ba_solve: every Jacobian evaluation is followed by k_freeze_jacobian
+  void set_frozen(const uint8_t* mask, int64_t count) {
+    const int B = 3 + hp.P, CB = hp.C * B;
+    std::vector<int32_t> idx;
+    std::vector<uint8_t> slot((size_t)CB, 0);
+    for (int64_t k = 0; k < count; ++k) {
+      if (!mask[k]) continue;
+      const int e = k < 3 * hp.C ? (int)(k % hp.C) * B + (int)(k / hp.C) : (int)((k - 3 * hp.C) / hp.P) * B + 3 + (int)((k - 3 * hp.C) % hp.P);
+      idx.push_back(e); slot[(size_t)e] = 1;
+    }
+    if (!idx.empty()) {
+      if (!frozen_idx) { frozen_idx = dalloc<int32_t>((size_t)CB); frozen_slot = dalloc<uint8_t>((size_t)CB); }
+      MVUS_HIP(hipMemcpyAsync(frozen_idx, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+      MVUS_HIP(hipMemcpyAsync(frozen_slot, slot.data(), slot.size(), hipMemcpyHostToDevice, stream));
+      MVUS_HIP(hipStreamSynchronize(stream));
+      frozen_mask.assign(mask, mask + count);
+    } else frozen_mask.clear();
+    frozen_count = (int)idx.size();
+  }
+  void freeze_jacobian() {
+    if (frozen_count <= 0 || dp.n_chunks <= 0) return;
+    if (hp.calib) hipLaunchKernelGGL(k_freeze_jacobian<30>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (const uint8_t*)frozen_slot, J);
+    else hipLaunchKernelGGL(k_freeze_jacobian<21>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (const uint8_t*)frozen_slot, J);
+    MVUS_HIP(hipGetLastError());
+  }
   // clr / clr_len: storage to zero beside the evaluation (HipSchur's normal-equation blocks); returns false if it was not done
   bool residual_sq(const double* x, double* f, double* out, double* clr = nullptr, int64_t clr_len = 0) {
     // (observation shards off the root rank: the replicated motion rows are rows of zeros there -- the general path)
@@ -560,6 +593,7 @@ struct HipBackend {
   }
   void jacobian(const double* x, double* f, int jac_mode) {
     if (jac_mode == MVUS_JAC_FD) jacobian_fd(x, f); else eval(x, f, true, jac_mode);
+    if (freeze_stored_jacobian) freeze_jacobian();      // (a solve with a mask in force: analytic, pattern and FD alike)
   }
 
   void set_fd_groups(const int32_t* groups, int ngroups) {
@@ -920,6 +954,13 @@ static void fit_smooth_pass(hipStream_t st, FitWork<T>& w, int ncoef, int n8, co
   fit_band_solve<4, T>(st, w, ncoef, w.Mx, cd, out, fail);
 }
 
+// a mask on a sharded handle (set in either order) refuses: it is never solved unmasked
+static bool frozen_on_shards(HipBackend& be, const char* who) {
+  if (be.frozen_count <= 0 || !(be.allreduce || be.tshard.on)) return false;
+  be.err = std::string(who) + ": frozen parameters (mvus_ba_set_frozen) are not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard)";
+  return true;
+}
+
 template <class F>
 static int guarded(mvus_ba* h, F&& fn) {
   if (!h) return MVUS_E_INVALID;
@@ -1091,6 +1132,7 @@ int mvus_ba_deterministic_fallback(mvus_ba* h, int32_t* fell_back) {
   return guarded(h, [&] {
     if (!fell_back) { h->be.err = "bad arguments"; return MVUS_E_INVALID; }
     *fell_back = (h->schur && h->schur->last_atomic) ? 1 : 0;
+    if (h->schur) h->schur->carry_held();
     return MVUS_OK;
   });
 }
@@ -1254,7 +1296,9 @@ int mvus_ba_jtu(mvus_ba* h, const double* u, double* z) {
 
 int mvus_ba_normal_equations(mvus_ba* h, double* g, double* JtJ_cam, double* band, double* cross, int32_t* W_out) {
   return guarded(h, [&] {
+    if (frozen_on_shards(h->be, "normal_equations")) return MVUS_E_UNSUPPORTED;
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(h->be));
+    h->schur->carry_held();
     return schur_export(h->be, *h->schur, g, JtJ_cam, band, cross, W_out);
   });
 }
@@ -1272,6 +1316,35 @@ int mvus_ba_set_loss(mvus_ba* h, int32_t loss, double f_scale) {
     return MVUS_OK;
   });
 }
+
+int mvus_ba_set_frozen(mvus_ba* h, const uint8_t* frozen, int64_t count) {
+  return guarded(h, [&] {
+    HipBackend& be = h->be;
+    const int64_t head = (int64_t)be.hp.C * (3 + be.hp.P);
+    if (frozen == nullptr || count == 0) count = 0;
+    else if (count != head) { be.err = "set_frozen: count must be C * (3 + P) = " + std::to_string(head) + ", not " + std::to_string(count); return MVUS_E_INVALID; }
+    bool any = false;
+    for (int64_t k = 0; k < count; ++k) {
+      if (frozen[k] > 1) { be.err = "set_frozen: frozen[" + std::to_string(k) + "] = " + std::to_string((int)frozen[k]) + " is neither 0 nor 1"; return MVUS_E_INVALID; }
+      any = any || frozen[k] != 0;
+    }
+    if (any && (be.allreduce || be.tshard.on)) {
+      be.err = "set_frozen: frozen parameters are not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard)";
+      return MVUS_E_UNSUPPORTED;
+    }
+    // what an LM solve left for its point -- cost, normal equations, the speculative linearisation it adopted -- belongs to the OLD set of
+    // unknowns: dropped (f(x) and the blocks are evaluated again); a changed set is another problem, so the damping starts where a fresh
+    // handle's does
+    be.carry = LmCarry{};
+    const std::vector<uint8_t> before = be.frozen_mask;
+    be.set_frozen(frozen, count);
+    if (be.frozen_mask != before) { be.lm_lambda = 0; be.lm_nu = 0; }
+    if (h->schur) h->schur->carry_held(false);      // (raw blocks of the held Jacobian stay usable; frozen ones belong to the old mask)
+    return MVUS_OK;
+  });
+}
+
+int64_t mvus_ba_num_frozen(const mvus_ba* h) { return h ? h->be.frozen_count : -1; }
 
 int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* weights_out) {
   return guarded(h, [&] {
@@ -1299,9 +1372,11 @@ int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
     HipBackend& be = h->be;
     if (!p_out || !(lambda >= 0)) { be.err = "lm_step: bad arguments"; return MVUS_E_INVALID; }
     if (!be.has_jacobian) { be.err = "no Jacobian held: call mvus_ba_residual_jacobian first"; return MVUS_E_INVALID; }
+    if (frozen_on_shards(be, "lm_step")) return MVUS_E_UNSUPPORTED;
     if (be.hp.C * (3 + be.hp.P) > 1152) throw HipError{"LM_SCHUR: reduced camera system larger than 1152 unknowns"};
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
     HipSchur<HipBackend>& sc = *h->schur;
+    sc.carry_held();
     sc.assemble_held(be);
     sc.solve_async(lambda);
     be.download(p_out, sc.step_ptr(), be.hp.n);          // synchronises
@@ -1323,7 +1398,14 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
       be.lb_fixed.assign(n, -INFINITY); be.ub_fixed.assign(n, INFINITY);
       if (be.hp.rs_bounds) for (int c = 0; c < be.hp.C; ++c) { be.lb_fixed[2 * be.hp.C + c] = 0.0; be.ub_fixed[2 * be.hp.C + c] = 1.0; }
     }
-    const std::vector<double>&lb = be.lb_fixed, &ub = be.ub_fixed;
+    // A held unknown has no box (both solvers): scipy's make_strictly_feasible would move an rs that sits ON its bound by 1e-10 before the
+    // first evaluation, and a held rs outside [0, 1] is the caller's business.  Without a mask: the handle's own vectors, as always.
+    std::vector<double> lbf, ubf;
+    if (be.frozen_count > 0 && be.hp.rs_bounds) {
+      lbf = be.lb_fixed; ubf = be.ub_fixed;
+      for (int64_t k = 0; k < (int64_t)be.frozen_mask.size(); ++k) if (be.frozen_mask[k]) { lbf[k] = -INFINITY; ubf[k] = INFINITY; }
+    }
+    const std::vector<double>&lb = lbf.empty() ? be.lb_fixed : lbf, &ub = ubf.empty() ? be.ub_fixed : ubf;
     SolveOptions so;
     so.jac_mode = opts->jac_mode; so.max_nfev = opts->max_nfev; so.ftol = opts->ftol; so.xtol = opts->xtol; so.gtol = opts->gtol;
     so.lsmr_atol = opts->lsmr_atol; so.lsmr_btol = opts->lsmr_btol; so.lsmr_conlim = opts->lsmr_conlim;
@@ -1344,6 +1426,7 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
                                                               : nullptr;
       if (what) { be.err = std::string("a robust loss (mvus_ba_set_loss) is not supported with ") + what + ": MVUS_SOLVER_LM_SCHUR with MVUS_JAC_ANALYTIC on one rank only"; return MVUS_E_UNSUPPORTED; }
     }
+    if (frozen_on_shards(be, "solve")) return MVUS_E_UNSUPPORTED;
     SolveResult sr;
     be.held_analytic_at_xcur = false;
     if (opts->solver == MVUS_SOLVER_LM_SCHUR) {
@@ -1359,6 +1442,13 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
       sr = lm_schur(be, *h->schur, x, lb, ub, so, be.f_cur);
       if (!sr.error) { be.lm_lambda = std::min(std::max(sr.lm_lambda, 1e-12), 1e6); be.lm_nu = std::min(sr.lm_nu, 1024.0); }
       if (sr.jac_stale) be.has_jacobian = false;      // mvus_ba_jv / jtu / lm_step must not pair J(x_old) with f(x_new)
+    }
+    else if (be.frozen_count > 0) {
+      // TRF + LSMR with a mask: the frozen slots of the stored Jacobian are zeroed behind every evaluation (analytic, pattern, FD), so
+      // g = J^T f, the LSMR solution started from zero and with them every step are exactly 0 there.
+      struct Flag { bool& f; explicit Flag(bool& b) : f(b) { f = true; } ~Flag() { f = false; } } on(be.freeze_stored_jacobian);
+      sr = trf_lsmr(be, xv, lb, ub, so, be.f_cur);
+      be.has_jacobian = false;      // (the stored Jacobian is the masked one: mvus_ba_jv / jtu / lm_step take error_BA's own)
     }
     else sr = trf_lsmr(be, xv, lb, ub, so, be.f_cur);
     const bool lm = opts->solver == MVUS_SOLVER_LM_SCHUR;

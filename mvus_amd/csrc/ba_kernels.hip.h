@@ -377,6 +377,23 @@ __global__ __launch_bounds__(kThreads) void k_j_export(DevProblem dp, const doub
   for (int r = 0; r < 2 * NS; ++r) Jout[(long long)r * dp.M + i] = Jc[r * kThreads];
 }
 
+// Frozen camera-side unknowns in the stored Jacobian (mvus_ba_set_frozen, TRF + LSMR): slot k of camera c is, in the chunk-major
+// layout, rows k and NS + k of every chunk of that camera.  slot_frozen[c * B + k] != 0 zeroes them (all kThreads lanes of the chunk:
+// the block is allocated in full); J v and J^T u then never move x[k].  Launched only with a non-empty mask.
+template <int NS>
+__global__ __launch_bounds__(kThreads) void k_freeze_jacobian(DevProblem dp, const uint8_t* __restrict__ slot_frozen, double* __restrict__ J) {
+  constexpr int B = NS - 12;
+  const int chunk = blockIdx.x;
+  if (chunk >= dp.n_chunks) return;
+  const uint8_t* __restrict__ fz = slot_frozen + dp.chunk_cam[chunk] * B;
+  double* __restrict__ Jc = J + j_chunk_offset<NS>(chunk) + threadIdx.x;
+  for (int k = 0; k < B; ++k) {
+    if (!fz[k]) continue;
+    Jc[k * kThreads] = 0.0;
+    Jc[(NS + k) * kThreads] = 0.0;
+  }
+}
+
 // y = J v on the detection rows.  Camera/sync entries of v are staged in LDS once per workgroup.
 // row j of the motion regulariser times v
 __device__ __forceinline__ double motion_row_times(const DevProblem& dp, const double* __restrict__ mJ, const int32_t* __restrict__ mctrl,

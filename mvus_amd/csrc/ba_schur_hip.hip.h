@@ -848,6 +848,31 @@ __global__ void k_ne_diag_grad(DevProblem dp, NEView ne, int raw, double* __rest
   ne_diag_grad_entry(dp, ne, raw, blockIdx.x * blockDim.x + threadIdx.x, D, gx);
 }
 
+// Frozen camera-side unknowns (mvus_ba_set_frozen): behind an assembly, before anything reads the blocks.  One workgroup per frozen
+// entry e = c * B + k (internal order: alpha, beta, rs, camera parameters): its cross row against the spline block, row and column k of
+// camera block c and its gradient entry become 0, the diagonal 1 -- D = diag(H) is extracted afterwards (k_band_pack / k_ne_diag_grad)
+// and comes out as 1, the damped system keeps (1 + lambda) p_k = 0 as an equation of its own and the step of that unknown is exactly 0.
+// The cross block is kept camera-major with the B slots of one (camera, spline row) adjacent, Et[(c * N3 + r) * B + k]: a cross ROW of
+// the exported layout is a column of stride B here, so each lane stores one double, B * 8 bytes from its neighbour's (N3 stores per
+// entry: 0.12 MB at configs[2]).  Two frozen entries of one camera write the same zeros into the two off-diagonal entries they share.
+// Launched only with a non-empty mask; never on a sharded handle (refused before).
+constexpr int kFreezeThreads = 256;
+__global__ __launch_bounds__(kFreezeThreads) void k_freeze_ne(NEView ne, const int32_t* __restrict__ frozen, int count) {
+  if ((int)blockIdx.x >= count) return;
+  const int e = frozen[blockIdx.x];
+  if (e < 0 || e >= ne.CB) return;
+  const int c = e / ne.B, k = e % ne.B;
+  double* __restrict__ col = ne.Et + (long long)c * ne.N3 * ne.B + k;
+  for (int r = threadIdx.x; r < ne.N3; r += kFreezeThreads) col[(long long)r * ne.B] = 0.0;
+  double* __restrict__ Ac = ne.A + (long long)c * ne.B * ne.B;
+  for (int t = threadIdx.x; t < ne.B; t += kFreezeThreads) {
+    const double v = t == k ? 1.0 : 0.0;
+    Ac[k * ne.B + t] = v;
+    Ac[t * ne.B + k] = v;
+  }
+  if (threadIdx.x == 0) ne.gc[e] = 0.0;
+}
+
 // ---- time shards: the blocks of the control points within `halo` of a cut receive rows from both neighbours --------
 // Packed exchange buffer: [boundary b = 1 .. world-1][2*halo control points from cut_b - halo][3*CB cross | W*9 band | 3 grad].
 // pack: this rank's partial blocks of its (<= 2) boundaries, everything else stays zero; after the sum over the ranks
@@ -3109,6 +3134,12 @@ struct HipSchur {
   }
   void assemble(BE&, const double* f_dev, const double* x_fused = nullptr, const int32_t* span_held = nullptr) {
     assemble_local(f_dev, x_fused, span_held);
+    // mvus_ba_set_frozen: every assembly -- window-major, detection-major, robust, the speculative one (the bound set is the one just
+    // written) -- is followed by the freeze pass; a handle without a mask launches nothing here
+    if (be.frozen_count > 0) {
+      hipLaunchKernelGGL(k_freeze_ne, dim3((unsigned)be.frozen_count), dim3(kFreezeThreads), 0, be.stream, ne, (const int32_t*)be.frozen_idx, be.frozen_count);
+      MVUS_HIP(hipGetLastError());
+    }
     if (shard) {
       // time shard: sum the camera blocks and the blocks of the control points near a cut; the cross block never moves
       // ... and diag(H), g in x order: every rank adds its PARTIAL sums (rows of a control point near a cut sit on two
@@ -3127,9 +3158,23 @@ struct HipSchur {
 
   // normal equations of the Jacobian the backend holds: the analytic Jacobian of x_cur goes through the fused window-major assembly
   // (the LM path's kernel; MVUS_NE_FROM_J=1 forms them from the stored blocks instead), anything else is assembled from J
+  // With a mask in force the blocks of the held Jacobian are assembled ONCE: if the call before this one on the handle left them here
+  // (held_seq, carried over mvus_ba_normal_equations / lm_step / set_frozen / deterministic_fallback only -- any other entry point
+  // lets it lapse), the masked system is those blocks with the freeze pass applied, entry for entry -- also behind the detection-major
+  // kernel, whose atomics would give a second assembly other last bits.  A handle without a mask assembles on every call, as always.
+  uint64_t held_seq = 0;
+  bool held_frozen = false, held_fused = false;
+  void carry_held(bool keep_frozen = true) { if (held_seq != 0 && held_seq + 1 == be.api_seq && (keep_frozen || !held_frozen)) held_seq = be.api_seq; }
   void assemble_held(BE&) {
     const bool fused = be.held_analytic_at_xcur && use_win && !std::getenv("MVUS_NE_FROM_J");
-    assemble(be, be.f_cur, fused ? be.x_cur : nullptr, fused ? be.span : nullptr);
+    if (be.frozen_count > 0 && held_seq == be.api_seq && held_fused == fused) {
+      if (!held_frozen) {
+        hipLaunchKernelGGL(k_freeze_ne, dim3((unsigned)be.frozen_count), dim3(kFreezeThreads), 0, be.stream, ne, (const int32_t*)be.frozen_idx, be.frozen_count);
+        MVUS_HIP(hipGetLastError());
+        diag_pending = true;
+      }
+    } else assemble(be, be.f_cur, fused ? be.x_cur : nullptr, fused ? be.span : nullptr);
+    held_seq = be.api_seq; held_frozen = be.frozen_count > 0; held_fused = fused;
   }
 
   void flush_diag() {
@@ -3273,6 +3318,9 @@ struct HipSchur {
   // to the scalars its fetch brings to the host (trial_follows), any other caller gets them by a copy to the same two slots
   bool fail_in_scalars() const { return shard; }
   const double* fail_sum_ptr() const { return shard ? px + be.hp.n : (const double*)nullptr; }
+  // READ-ONLY on the assembled blocks (A, gc, Cb, gs, Et of the bound set): everything a solve writes is its own workspace (Lb, Z, G, S,
+  // the separator buffers, D / gx, px).  assemble_held relies on that -- a masked inspection call reuses the blocks an earlier call left
+  // behind -- and so does a rejected trial, whose next solve reads the same blocks at another lambda.  Keep it so.
   void solve_async(double lambda, bool trial_follows = false) {
     RoctxRange range("mvus schur solve");
     const long long nLb = (long long)ne.N3 * (BW + 1);

@@ -33,6 +33,13 @@ Extra ``settings`` keys (all optional; a reference ``config.json`` has none of t
                pixels) arguments of scipy's least_squares, which the reference never passes: gross outliers stop pulling on the first
                BA, the one that runs before ``remove_outliers`` can cut them.  Not with 'trf' (ValueError), and a problem the
                wide-band policy above would hand to TRF raises instead of dropping the loss.
+``ba_freeze``  {camera index: [names]} with names from 'alpha', 'beta', 'rs', 'R', 't', 'K', 'd': those parameters of that camera are held
+               constant during BA (``mvus_ba_set_frozen``; both solvers).  'K' and 'd' need ``opt_calib`` (they are not parameters
+               otherwise); cameras outside the BA's ``sequence[:numCam]`` are ignored for that BA.  The reference can only switch a
+               group off for every camera at once (``opt_sync``, ``rs``, ``opt_calib``).
+``ba_gauge``   'free' (DEFAULT: the reference's problem, similarity gauge left to the solver) or 'anchor': the pose of ``sequence[0]`` and
+               one translation component of ``sequence[1]`` are held -- the seven degrees of freedom of the similarity, no more
+               (``Scene.ba_frozen_mask``).
 ``ba_deterministic`` accepted and ignored: the 'lm' solver's normal equations are assembled without floating-point atomics
                (one writer, one order of additions per entry) -- the same bits on every run by construction.
 ``opt_sync`` (reference key: False freezes alpha/beta), ``device``.
@@ -439,6 +446,11 @@ class Scene:
         h = self._resident_handle(prob, cams)      # stays resident for remove_outliers and the next BA
         if h.loss != (loss, f_scale):              # (a handle that has the loss already keeps what its last solve carried over)
             h.set_loss(loss, f_scale)
+        if 'ba_freeze' in st or 'ba_gauge' in st or h.num_frozen:
+            # held parameters (ba_freeze, ba_gauge): state of the handle like the loss, so the TRF hand-over below solves with them too
+            mask, cur = self.ba_frozen_mask(cams), h.frozen
+            if not np.array_equal(mask, cur if cur is not None else np.zeros(mask.size, dtype=bool)):
+                h.set_frozen(mask)
         opts = _ba._lib.default_opts(solver, jac_mode, max_iter)
         opts.lm_lambda_min = float(st.get('ba_lambda_min', opts.lm_lambda_min))
         opts.lm_trust_radius = float(st.get('ba_trust_radius', opts.lm_trust_radius))
@@ -465,6 +477,7 @@ class Scene:
             opts = _ba._lib.default_opts(_ba.SOLVER_TRF_LSMR, _ba.JAC_ANALYTIC, max_iter)
             res = h.solve(model, opts=opts, ties='canonical')
             res.solver_used = 'trf (fallback from lm: %s)' % e
+        res.num_frozen = h.num_frozen
         alpha, beta, rs_new, cam_states, coefs = _problem.unpack_x(prob, res.x)
         self.alpha[cams], self.beta[cams], self.rs[cams] = alpha, beta, rs_new
         for k, i in enumerate(cams):
@@ -496,7 +509,73 @@ class Scene:
         if jac not in modes:
             raise ValueError("settings['ba_jacobian'] must be one of %s, not %r" % (sorted(modes), jac))
         self.ba_loss()                       # (validated with the rest: a bad ba_loss / ba_f_scale raises before any GPU call)
+        self.ba_freeze()                     # (and ba_freeze / ba_gauge)
         return solver, modes[jac]
+
+    FREEZE_NAMES = ('alpha', 'beta', 'rs', 'R', 't', 'K', 'd')
+
+    def ba_freeze(self):
+        """({camera index: names}, gauge) of settings['ba_freeze'] / settings['ba_gauge'], validated: host only, raises ValueError before
+        any GPU call.  Without the keys: ({}, 'free') -- the reference's problem."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        gauge = st.get('ba_gauge', 'free')
+        if not isinstance(gauge, str) or gauge not in ('free', 'anchor'):
+            raise ValueError("settings['ba_gauge'] must be 'free' or 'anchor', not %r" % (gauge,))
+        raw = st.get('ba_freeze', {})
+        if raw is None:
+            raw = {}
+        if not isinstance(raw, dict):
+            raise ValueError("settings['ba_freeze'] must map camera indices to lists of names from %s, not %r" % (list(self.FREEZE_NAMES), raw))
+        freeze = {}
+        for key, names in raw.items():
+            try:                                 # (a config.json has string keys)
+                cam = int(key)
+                if isinstance(key, (bool, float)) or str(cam) != str(key).strip():
+                    raise ValueError
+            except (TypeError, ValueError):
+                raise ValueError("settings['ba_freeze']: %r is not a camera index" % (key,)) from None
+            if cam < 0:
+                raise ValueError("settings['ba_freeze']: %r is not a camera index" % (key,))
+            if isinstance(names, str) or not isinstance(names, (list, tuple, set, frozenset)):
+                raise ValueError("settings['ba_freeze'][%r] must be a list of names from %s, not %r" % (key, list(self.FREEZE_NAMES), names))
+            for name in names:
+                if not isinstance(name, str) or name not in self.FREEZE_NAMES:
+                    raise ValueError("settings['ba_freeze'][%r]: unknown name %r (one of %s)" % (key, name, list(self.FREEZE_NAMES)))
+                if name in ('K', 'd') and not st.get('opt_calib', False):
+                    raise ValueError("settings['ba_freeze'][%r]: %r is a parameter only with settings['opt_calib'] (fixed calibration is not in x)" % (key, name))
+            freeze.setdefault(cam, set()).update(names)
+        return freeze, gauge
+
+    def ba_frozen_mask(self, cams):
+        """bool[C * (3 + P)] over the camera-side head of x (pack_x order: alpha(C), beta(C), rs(C), P parameters per camera) for a BA over
+        ``cams``: what settings['ba_freeze'] names, plus -- settings['ba_gauge'] = 'anchor' -- the trivial gauge: the six pose parameters of
+        cams[0] and component k = argmax |R_1 (C_0 - C_1)| of the translation of cams[1].  That vector is d t_1 / d s of a scaling of the
+        scene about the first camera's centre C_0 (t_1 = -R_1 C_1, C_1 -> C_0 + s (C_1 - C_0)): with the first pose held the similarity has
+        only that scaling left, and holding a component it moves removes it.  Pure host function; no GPU call."""
+        freeze, gauge = self.ba_freeze()
+        st = self.settings if isinstance(self.settings, dict) else {}
+        cams = list(cams)
+        C = len(cams)
+        calib = bool(st.get('opt_calib', False))
+        P = 15 if calib else 6                    # fx fy cx cy | rvec | t | k1 k2 p1 p2 k3  or  rvec | t  (Camera.P2vector)
+        part = {'K': range(0, 4), 'R': range(4, 7), 't': range(7, 10), 'd': range(10, 15)} if calib else {'R': range(0, 3), 't': range(3, 6)}
+        mask = np.zeros(C * (3 + P), dtype=bool)
+        for k, cam in enumerate(cams):
+            for name in freeze.get(int(cam), ()):
+                if name in ('alpha', 'beta', 'rs'):
+                    mask[('alpha', 'beta', 'rs').index(name) * C + k] = True
+                else:
+                    mask[[3 * C + k * P + j for j in part[name]]] = True
+        if gauge == 'anchor' and C >= 1:
+            mask[[3 * C + j for j in list(part['R']) + list(part['t'])]] = True
+            if C >= 2:
+                c0, c1 = self.cameras[cams[0]], self.cameras[cams[1]]
+                R0, R1 = np.asarray(c0.R, dtype=np.float64), np.asarray(c1.R, dtype=np.float64)
+                centre0 = -R0.T @ np.ravel(np.asarray(c0.t, dtype=np.float64))
+                centre1 = -R1.T @ np.ravel(np.asarray(c1.t, dtype=np.float64))
+                comp = int(np.argmax(np.abs(R1 @ (centre0 - centre1))))
+                mask[3 * C + P + part['t'][comp]] = True
+        return mask
 
     def ba_loss(self):
         """(MVUS_LOSS_* code, f_scale) of settings['ba_loss'] / settings['ba_f_scale']: the ``loss`` and ``f_scale`` arguments of

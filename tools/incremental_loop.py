@@ -3,7 +3,7 @@
 detections, rolling shutter, motion regulariser F -- 12 BAs, 6 outlier passes and 5 x (select_most_overlap, get_camera_pose,
 triangulate + refit), starting from two posed cameras and their common piece of trajectory.
 
-    python tools/incremental_loop.py [--obs 100000] [--solver trf|lm] [--max-iter 10] [--cpu-sample]
+    python tools/incremental_loop.py [--obs 100000] [--solver trf|lm] [--max-iter 10] [--gauge anchor] [--cpu-sample]
 
 Prints the wall-clock split per stage (the reference's only own performance figure is this loop's "Total time",
 main.py:68,81), the final per-camera reprojection error, the inlier bookkeeping against the generator's labels and the
@@ -35,6 +35,7 @@ def main():
     ap.add_argument('--lambda-min', type=float, default=None, help="settings['ba_lambda_min'] (floor of the LM damping)")
     ap.add_argument('--trust-radius', type=float, default=None, help="settings['ba_trust_radius']: 0 = scipy's Delta_0 = |x0|, > 0 that radius, < 0 none")
     ap.add_argument('--lm-wide', choices=['lm', 'trf'], default=None, help="settings['ba_lm_wide_band']: what ba_solver=lm does when the motion rows reach over more than six control points")
+    ap.add_argument('--gauge', choices=['free', 'anchor'], default=None, help="settings['ba_gauge']: 'anchor' holds the pose of sequence[0] and one translation component of sequence[1] in every BA (the similarity gauge)")
     args = ap.parse_args()
     from mvus_amd import pipeline, synth
     kw = dict(synth.BASELINE_CONFIGS[1])
@@ -47,6 +48,7 @@ def main():
     if args.lambda_min is not None: st_extra['ba_lambda_min'] = args.lambda_min
     if args.lm_wide is not None: st_extra['ba_lm_wide_band'] = args.lm_wide
     if args.trust_radius is not None: st_extra['ba_trust_radius'] = args.trust_radius
+    if args.gauge is not None: st_extra['ba_gauge'] = args.gauge
     flight, sc = pipeline.staged_scene(nc, nobs, seed=seed, settings=st_extra, perturb=0.3, **kw)
     print('scene: %d cameras, %d detections (%s), start trajectory %.0f..%.0f of 0..%.0f, %d control points; set-up %.2f s'
           % (nc, sum(d.shape[1] for d in flight.detections), [d.shape[1] for d in flight.detections], flight.spline['int'][0, 0],
