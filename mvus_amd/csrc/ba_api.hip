@@ -1,4 +1,5 @@
-// libmvusba.so: HIP backend of the templated optimiser + the C ABI of include/mvus_ba.h.
+// libmvusba.so, bundle adjustment: HIP backend of the templated optimiser + the mvus_ba_* part of the C ABI of include/mvus_ba.h
+// (the spline stage is spline_api.hip, two-view geometry and PnP twoview_api.hip; api_common.h is what the three share).
 // There is no CPU compute path in this library: every entry point that evaluates anything
 // launches HIP kernels, and mvus_ba_create fails with MVUS_E_HIP when no device is usable.
 #include <hip/hip_runtime.h>
@@ -18,13 +19,11 @@
 #include "ba_problem.h"
 #include "ba_solver.h"
 #include "ba_schur_hip.hip.h"
-#include "triangulate.hip.h"
-#include "spline_ops.hip.h"
-#include "spline_fit.hip.h"
-#include "pnp.hip.h"
-#include "epipolar.hip.h"
+#include "ba_schur_host.hip.h"
 
 namespace mvus {
+
+thread_local std::string g_create_error;      // declared in api_common.h: the one error string behind mvus_last_error(NULL)
 
 static inline int grid_for(long long len) { return (int)std::min<long long>(2048, std::max<long long>(1, (len + kThreads - 1) / kThreads)); }
 
@@ -447,13 +446,10 @@ struct HipBackend {
     ensure_cams(x);
     if (dp.n_chunks > 0) {
       const dim3 g(dp.n_chunks), gj(xcd_grid(dp.n_chunks)), b(kThreads);
-      if (hp.calib) {
-        if (jac) hipLaunchKernelGGL((k_observations<true, true>), gj, b, 0, stream, dp, cams, x, f, J, span, pat0, (int)masked);
-        else hipLaunchKernelGGL((k_observations<true, false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0);
-      } else {
-        if (jac) hipLaunchKernelGGL((k_observations<false, true>), gj, b, 0, stream, dp, cams, x, f, J, span, pat0, (int)masked);
-        else hipLaunchKernelGGL((k_observations<false, false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0);
-      }
+      with_flag(hp.calib, [&](auto calib) {
+        if (jac) hipLaunchKernelGGL((k_observations<calib(), true>), gj, b, 0, stream, dp, cams, x, f, J, span, pat0, (int)masked);
+        else hipLaunchKernelGGL((k_observations<calib(), false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0);
+      });
       if (!jac) rspan_for = x;
     }
     if (hp.T > 0) {
@@ -534,8 +530,7 @@ struct HipBackend {
   }
   void freeze_jacobian() {
     if (frozen_count <= 0 || dp.n_chunks <= 0) return;
-    if (hp.calib) hipLaunchKernelGGL(k_freeze_jacobian<30>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (const uint8_t*)frozen_slot, J);
-    else hipLaunchKernelGGL(k_freeze_jacobian<21>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (const uint8_t*)frozen_slot, J);
+    with_flag(hp.calib, [&](auto calib) { hipLaunchKernelGGL(k_freeze_jacobian<calib() ? 30 : 21>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (const uint8_t*)frozen_slot, J); });
     MVUS_HIP(hipGetLastError());
   }
   // clr / clr_len: storage to zero beside the evaluation (HipSchur's normal-equation blocks); returns false if it was not done
@@ -565,13 +560,10 @@ struct HipBackend {
       const int fb = (clr && clr_len > 0) ? (int)std::min<int64_t>(2048, (clr_len + kThreads - 1) / kThreads) : 0;
       const dim3 g(dp.n_chunks + fb), b(kThreads);
       double* c = fb > 0 ? clr : (double*)nullptr;
-      if (robust()) {
-        if (hp.calib) hipLaunchKernelGGL((k_observations<true, false, true>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len, loss);
-        else hipLaunchKernelGGL((k_observations<false, false, true>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len, loss);
-      } else {
-        if (hp.calib) hipLaunchKernelGGL((k_observations<true, false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len);
-        else hipLaunchKernelGGL((k_observations<false, false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len);
-      }
+      with_flag(hp.calib, [&](auto calib) {
+        if (robust()) hipLaunchKernelGGL((k_observations<calib(), false, true>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len, loss);
+        else hipLaunchKernelGGL((k_observations<calib(), false>), g, b, 0, stream, dp, cams, x, f, J, rspan, pat0, 0, sq_part, c, (long long)clr_len);
+      });
       rspan_for = x;
       cleared = fb > 0;
     }
@@ -615,10 +607,8 @@ struct HipBackend {
       hipLaunchKernelGGL(k_fd_perturb, dim3((n + 255) / 256), dim3(256), 0, stream, n, g, x, fd_h, fd_groups, fd_xg);
       eval(fd_xg, fd_F + (size_t)g * hp.m, false, 0);
     }
-    if (dp.n_chunks > 0) {
-      if (hp.calib) hipLaunchKernelGGL(k_fd_fill<30>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (long long)hp.m, f, fd_F, fd_dx, fd_groups, pat0, J, span);
-      else hipLaunchKernelGGL(k_fd_fill<21>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (long long)hp.m, f, fd_F, fd_dx, fd_groups, pat0, J, span);
-    }
+    if (dp.n_chunks > 0)
+      with_flag(hp.calib, [&](auto calib) { hipLaunchKernelGGL(k_fd_fill<calib() ? 30 : 21>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (long long)hp.m, f, fd_F, fd_dx, fd_groups, pat0, J, span); });
     if (hp.T > 0) {
       if (is_root) hipLaunchKernelGGL(k_fd_fill_motion, dim3((hp.T + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, dp, (long long)hp.m, f, fd_F, fd_dx, fd_groups, mJ, mctrl);
     }
@@ -723,8 +713,7 @@ struct HipBackend {
     if (dp.n_chunks > 0) {
       const unsigned grid = (unsigned)(xcd_grid(dp.n_chunks) + (fused ? (hp.T + kThreads - 1) / kThreads : 0));
       const double* mj = fused ? mJ : nullptr;
-      if (hp.calib) hipLaunchKernelGGL(k_jv<30>, dim3(grid), dim3(kThreads), 0, stream, dp, J, span, v, y, mj, mctrl, y + 2 * hp.M);
-      else hipLaunchKernelGGL(k_jv<21>, dim3(grid), dim3(kThreads), 0, stream, dp, J, span, v, y, mj, mctrl, y + 2 * hp.M);
+      with_flag(hp.calib, [&](auto calib) { hipLaunchKernelGGL(k_jv<calib() ? 30 : 21>, dim3(grid), dim3(kThreads), 0, stream, dp, J, span, v, y, mj, mctrl, y + 2 * hp.M); });
     }
     if (hp.T > 0 && !fused) hipLaunchKernelGGL(k_motion_jv, dim3((hp.T + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, dp, mJ, mctrl, v, y + 2 * hp.M);
     MVUS_HIP(hipGetLastError());
@@ -752,17 +741,13 @@ struct HipBackend {
     if (!reuse_index) MVUS_HIP(hipMemsetAsync(jt_bounds, 0, 2 * sizeof(int), stream));
     const dim3 g2(hp.C + (hp.N + kThreads / 64 - 1) / (kThreads / 64)), b(kThreads);
     const int motion = hp.T > 0 ? 1 : 0;
-    if (hp.calib) {
-      if (dp.n_chunks > 0) hipLaunchKernelGGL(k_jtu_partial<30>, dim3(xcd_grid(dp.n_chunks)), b, 0, stream, dp, J, span, u, z, zc, zs, zg0, jt_nondet, zext);
+    with_flag(hp.calib, [&](auto calib) {
+      constexpr int NS = calib() ? 30 : 21;
+      if (dp.n_chunks > 0) hipLaunchKernelGGL(k_jtu_partial<NS>, dim3(xcd_grid(dp.n_chunks)), b, 0, stream, dp, J, span, u, z, zc, zs, zg0, jt_nondet, zext);
       if (!reuse_index) hipLaunchKernelGGL(k_jtu_index, dim3(hp.C), dim3(64), 0, stream, dp, zg0, zfill, zext, jt_bounds);
       if (build_first) build_jt_first();
-      hipLaunchKernelGGL(k_jtu_reduce<30>, g2, b, 0, stream, dp, zc, zs, zg0, zfill, mJ, mctrl, u + 2 * hp.M, motion, z, (reuse_index || build_first) ? jt_first : (int32_t*)nullptr, jt_bounds);
-    } else {
-      if (dp.n_chunks > 0) hipLaunchKernelGGL(k_jtu_partial<21>, dim3(xcd_grid(dp.n_chunks)), b, 0, stream, dp, J, span, u, z, zc, zs, zg0, jt_nondet, zext);
-      if (!reuse_index) hipLaunchKernelGGL(k_jtu_index, dim3(hp.C), dim3(64), 0, stream, dp, zg0, zfill, zext, jt_bounds);
-      if (build_first) build_jt_first();
-      hipLaunchKernelGGL(k_jtu_reduce<21>, g2, b, 0, stream, dp, zc, zs, zg0, zfill, mJ, mctrl, u + 2 * hp.M, motion, z, (reuse_index || build_first) ? jt_first : (int32_t*)nullptr, jt_bounds);
-    }
+      hipLaunchKernelGGL(k_jtu_reduce<NS>, g2, b, 0, stream, dp, zc, zs, zg0, zfill, mJ, mctrl, u + 2 * hp.M, motion, z, (reuse_index || build_first) ? jt_first : (int32_t*)nullptr, jt_bounds);
+    });
     MVUS_HIP(hipGetLastError());
   }
   void build_jt_first() {
@@ -821,11 +806,12 @@ struct HipBackend {
         if (one_pass) {
           const dim3 g2(hp.C + (hp.N + kThreads / 64 - 1) / (kThreads / 64)), bt(kThreads);
           const int motion = hp.T > 0 ? 1 : 0;
-          if (hp.calib) hipLaunchKernelGGL(k_jvjtu<30>, dim3(gj), bt, 0, stream, dp, J, span, v, ut, c, ubeta, lsmr_pu, tn, zc, zs, zg0, jt_nondet, zext, mJ, mctrl);
-          else hipLaunchKernelGGL(k_jvjtu<21>, dim3(gj), bt, 0, stream, dp, J, span, v, ut, c, ubeta, lsmr_pu, tn, zc, zs, zg0, jt_nondet, zext, mJ, mctrl);
-          if (launched == 0) { hipLaunchKernelGGL(k_jtu_index, dim3(hp.C), dim3(64), 0, stream, dp, zg0, zfill, zext, jt_bounds); build_jt_first(); }
-          if (hp.calib) hipLaunchKernelGGL(k_jtu_reduce<30>, g2, bt, 0, stream, dp, zc, zs, zg0, zfill, mJ, mctrl, ut + 2 * hp.M, motion, tn, jt_first, jt_bounds);
-          else hipLaunchKernelGGL(k_jtu_reduce<21>, g2, bt, 0, stream, dp, zc, zs, zg0, zfill, mJ, mctrl, ut + 2 * hp.M, motion, tn, jt_first, jt_bounds);
+          with_flag(hp.calib, [&](auto calib) {
+            constexpr int NS = calib() ? 30 : 21;
+            hipLaunchKernelGGL(k_jvjtu<NS>, dim3(gj), bt, 0, stream, dp, J, span, v, ut, c, ubeta, lsmr_pu, tn, zc, zs, zg0, jt_nondet, zext, mJ, mctrl);
+            if (launched == 0) { hipLaunchKernelGGL(k_jtu_index, dim3(hp.C), dim3(64), 0, stream, dp, zg0, zfill, zext, jt_bounds); build_jt_first(); }
+            hipLaunchKernelGGL(k_jtu_reduce<NS>, g2, bt, 0, stream, dp, zc, zs, zg0, zfill, mJ, mctrl, ut + 2 * hp.M, motion, tn, jt_first, jt_bounds);
+          });
           hipLaunchKernelGGL(k_lsmr_v1, dim3(gn), dim3(kThreads), 0, stream, n, tn, v, c, (int)gj, lsmr_pu, beta_dev, ubeta, pv);
         } else if (scaled) {
         // the bounded problem: A = [J diag(D); diag(E)] -- the host-driven loop's operations (Lsmr::run), launch for launch without its
@@ -874,85 +860,6 @@ struct mvus_ba {
   mvus_rccl_handle rccl;                         // communicator of mvus_ba_set_rccl (destroyed with the handle)
   ~mvus_ba();
 };
-
-static thread_local std::string g_create_error;
-
-// stateless helpers share this: device buffers of one call, freed on every exit
-namespace {
-struct CallBuffers {
-  std::vector<void*> bufs;
-  hipStream_t st = nullptr;
-  void open(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) throw HipError{"no usable HIP device (libmvusba has no CPU fallback)"};
-    MVUS_HIP(hipSetDevice(device));
-    MVUS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  }
-  template <class T>
-  T* get(size_t count) { void* p = nullptr; MVUS_HIP(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T))); bufs.push_back(p); return static_cast<T*>(p); }
-  template <class T>
-  T* put(const T* host, size_t count) { T* d = get<T>(count); if (count) MVUS_HIP(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, st)); return d; }
-  ~CallBuffers() { for (void* p : bufs) (void)hipFree(p); if (st) (void)hipStreamDestroy(st); }
-};
-}  // namespace
-
-
-// device work arrays of the smoothing fit in one precision (double, or double-double for ill-conditioned knot sets)
-template <class T>
-struct FitWork {
-  T *SB = nullptr, *G5 = nullptr, *BtB = nullptr, *Mx = nullptr, *Lf = nullptr, *rhs = nullptr, *yw = nullptr, *YL = nullptr, *parts = nullptr;
-  bool ready = false, penalty = false;
-  void alloc(CallBuffers& cb, size_t nest) {
-    if (ready) return;
-    SB = cb.get<T>((size_t)kFitBlk * (nest + kFitSliceBlocks)); G5 = cb.get<T>(5 * nest); BtB = cb.get<T>(5 * nest); Mx = cb.get<T>(5 * nest);
-    const size_t rows = nest + kBandPartsMax;            // the transposed copies hold length(0) rows for EVERY interior
-    Lf = cb.get<T>(5 * rows); rhs = cb.get<T>(3 * nest); yw = cb.get<T>(3 * rows);
-    YL = cb.get<T>(4 * rows); parts = cb.get<T>((size_t)kBandPartsWork);
-    ready = true;
-  }
-};
-// systems of at least this many rows go to k_band_solve_parts (MVUS_BAND_PARTS_MIN: the tests push the small fixtures through it too)
-static int band_parts_min() {
-  static const int v = [] { const char* e = std::getenv("MVUS_BAND_PARTS_MIN"); return e ? std::max(16, std::atoi(e)) : 192; }();
-  return v;
-}
-// banded solve of the pass; returns true when the factor's diagonal in out[0] is FITPACK's (one chain in the natural order)
-template <int HB, class T>
-static bool fit_band_solve(hipStream_t st, FitWork<T>& w, int ncoef, const T* Mband, double* cd, double* out, int* fail) {
-  const BandParts bp = band_parts(ncoef, HB, band_parts_min());
-  if (bp.P < 2) {
-    hipLaunchKernelGGL((k_band_solve<HB, T>), dim3(1), dim3(64), 0, st, ncoef, Mband, w.rhs, w.Lf, w.yw, cd, out, fail);
-    return true;
-  }
-  hipLaunchKernelGGL((k_band_solve_parts<HB, T>), dim3(1), dim3(64 * ((bp.P + 63) / 64)), 0, st, ncoef, bp, Mband, w.rhs, w.Lf, w.yw, w.YL, w.parts, cd, out, fail);
-  return false;
-}
-static dim3 fit_blocks(long long cnt) { return dim3((unsigned)((cnt + 255) / 256)); }
-// least-squares spline on the current knots: normal equations from the span blocks, banded Cholesky, coefficients -> cd
-template <class T>
-static bool fit_lsq_pass(hipStream_t st, FitWork<T>& w, long long m, const long long* first, const double* q, const double* dX, int ncoef, int nrint,
-                         double* cd, double* out, int* fail) {
-  constexpr int NT = sizeof(T) == sizeof(double) ? 256 : 64;
-  const int nslice = fit_slices(nrint);
-  hipLaunchKernelGGL((k_fit_blocks<T, NT>), dim3(nrint, nslice), dim3(NT), 0, st, m, first, q, dX, w.SB);
-  if (nslice > 1) hipLaunchKernelGGL(k_fit_slice_sum<T>, fit_blocks((long long)nrint * kFitBlk), dim3(256), 0, st, (long long)nrint * kFitBlk, nslice, w.SB);
-  hipLaunchKernelGGL(k_fit_band<T>, fit_blocks(ncoef), dim3(256), 0, st, ncoef, nrint, w.SB, w.G5, w.rhs, band_parts(ncoef, 3, band_parts_min()), w.Lf, w.yw);
-  w.penalty = false;
-  return fit_band_solve<3, T>(st, w, ncoef, w.G5, cd, out, fail);
-}
-// the sum of the factor's diagonal in the natural elimination order (fppara's initial p) when the last pass was partitioned
-template <class T>
-static void fit_lsq_diag(hipStream_t st, FitWork<T>& w, int ncoef, double* out) {
-  hipLaunchKernelGGL((k_band_diag_sum<3, T>), dim3(1), dim3(64), 0, st, ncoef, w.G5, out);
-}
-// smoothing spline for one value of p on the same knots (fit_lsq_pass has run in this precision)
-template <class T>
-static void fit_smooth_pass(hipStream_t st, FitWork<T>& w, int ncoef, int n8, const double* bd, double pinv, double* cd, double* out, int* fail) {
-  if (!w.penalty) { hipLaunchKernelGGL(k_fit_penalty<T>, fit_blocks(ncoef), dim3(256), 0, st, ncoef, n8, bd, w.BtB); w.penalty = true; }
-  hipLaunchKernelGGL(k_fit_combine<T>, fit_blocks(5ll * ncoef), dim3(256), 0, st, 5ll * ncoef, w.G5, w.BtB, pinv, w.Mx, ncoef, w.rhs,
-                     band_parts(ncoef, 4, band_parts_min()), w.Lf, w.yw);
-  fit_band_solve<4, T>(st, w, ncoef, w.Mx, cd, out, fail);
-}
 
 // a mask on a sharded handle (set in either order) refuses: it is never solved unmasked
 static bool frozen_on_shards(HipBackend& be, const char* who) {
@@ -1060,10 +967,8 @@ int mvus_ba_residual_jacobian(mvus_ba* h, const double* x, int32_t jac_mode, dou
       PoolGuard<HipBackend> pool(be);
       double* Jout = pool.get((int64_t)2 * be.hp.NS * std::max<int64_t>(be.hp.M, 1));
       MVUS_HIP(hipMemsetAsync(Jout, 0, sizeof(double) * 2 * be.hp.NS * be.hp.M, be.stream));
-      if (be.dp.n_chunks > 0) {
-        if (be.hp.calib) hipLaunchKernelGGL(k_j_export<30>, dim3(be.dp.n_chunks), dim3(kThreads), 0, be.stream, be.dp, be.J, Jout);
-        else hipLaunchKernelGGL(k_j_export<21>, dim3(be.dp.n_chunks), dim3(kThreads), 0, be.stream, be.dp, be.J, Jout);
-      }
+      if (be.dp.n_chunks > 0)
+        with_flag(be.hp.calib, [&](auto calib) { hipLaunchKernelGGL(k_j_export<calib() ? 30 : 21>, dim3(be.dp.n_chunks), dim3(kThreads), 0, be.stream, be.dp, be.J, Jout); });
       be.download(J, Jout, (int64_t)2 * be.hp.NS * be.hp.M);
     }
     if (ctrl) {
@@ -1691,21 +1596,18 @@ int mvus_ba_time_kernel(mvus_ba* h, int32_t which, int32_t launches, double* avg
       switch (which) {
         case 0:
           if (be.robust()) { be.residual_sq(be.x_cur, be.f_cur, be.scal_dev + 3); break; }      // (the cost evaluation of a robust LM trial: + motion rows and the final sum)
-          if (be.hp.calib) hipLaunchKernelGGL((k_observations<true, false>), g, b, 0, be.stream, be.dp, be.cams, be.x_cur, be.f_cur, be.J, be.rspan, be.pat0, 0);
-          else hipLaunchKernelGGL((k_observations<false, false>), g, b, 0, be.stream, be.dp, be.cams, be.x_cur, be.f_cur, be.J, be.rspan, be.pat0, 0);
+          with_flag(be.hp.calib, [&](auto calib) { hipLaunchKernelGGL((k_observations<calib(), false>), g, b, 0, be.stream, be.dp, be.cams, be.x_cur, be.f_cur, be.J, be.rspan, be.pat0, 0); });
           break;
         case 1:
         case 5: {
           const OutSet& o = sets[turn];
           turn = (turn + 1) % (int)sets.size();
           const dim3 gj(xcd_grid(be.dp.n_chunks));
-          if (be.hp.calib) hipLaunchKernelGGL((k_observations<true, true>), gj, b, 0, be.stream, be.dp, be.cams, be.x_cur, o.f, o.J, o.span, be.pat0, 0);
-          else hipLaunchKernelGGL((k_observations<false, true>), gj, b, 0, be.stream, be.dp, be.cams, be.x_cur, o.f, o.J, o.span, be.pat0, 0);
+          with_flag(be.hp.calib, [&](auto calib) { hipLaunchKernelGGL((k_observations<calib(), true>), gj, b, 0, be.stream, be.dp, be.cams, be.x_cur, o.f, o.J, o.span, be.pat0, 0); });
           break;
         }
         case 2:
-          if (be.hp.calib) hipLaunchKernelGGL(k_jv<30>, dim3(xcd_grid(be.dp.n_chunks)), b, 0, be.stream, be.dp, be.J, be.span, vn, ym);
-          else hipLaunchKernelGGL(k_jv<21>, dim3(xcd_grid(be.dp.n_chunks)), b, 0, be.stream, be.dp, be.J, be.span, vn, ym);
+          with_flag(be.hp.calib, [&](auto calib) { hipLaunchKernelGGL(k_jv<calib() ? 30 : 21>, dim3(xcd_grid(be.dp.n_chunks)), b, 0, be.stream, be.dp, be.J, be.span, vn, ym); });
           break;
         case 3:
           be.jtu_local(um, zn);
@@ -1737,821 +1639,4 @@ int mvus_ba_time_kernel(mvus_ba* h, int32_t which, int32_t launches, double* avg
     return MVUS_OK;
   });
 }
-
-int mvus_triangulate(int32_t device, int64_t N, const double* x1, const double* x2, const double* P1, const double* P2,
-                     double* X, double* err1, double* err2) {
-  if (N < 0 || !P1 || !P2 || (N > 0 && (!x1 || !x2 || !X))) { g_create_error = "triangulate: bad arguments"; return MVUS_E_INVALID; }
-  if (N == 0) return MVUS_OK;
-  double *dx1 = nullptr, *dx2 = nullptr, *dX = nullptr, *de = nullptr;
-  hipStream_t st = nullptr;
-  auto cleanup = [&]() { (void)hipFree(dx1); (void)hipFree(dx2); (void)hipFree(dX); (void)hipFree(de); if (st) (void)hipStreamDestroy(st); };
-  try {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) throw HipError{"no usable HIP device (libmvusba has no CPU fallback)"};
-    MVUS_HIP(hipSetDevice(device));
-    MVUS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    const size_t b2 = sizeof(double) * 2 * (size_t)N;
-    MVUS_HIP(hipMalloc(reinterpret_cast<void**>(&dx1), b2)); MVUS_HIP(hipMalloc(reinterpret_cast<void**>(&dx2), b2));
-    MVUS_HIP(hipMalloc(reinterpret_cast<void**>(&dX), 2 * b2)); MVUS_HIP(hipMalloc(reinterpret_cast<void**>(&de), b2));
-    MVUS_HIP(hipMemcpyAsync(dx1, x1, b2, hipMemcpyHostToDevice, st));
-    MVUS_HIP(hipMemcpyAsync(dx2, x2, b2, hipMemcpyHostToDevice, st));
-    TriCams cams;
-    std::memcpy(cams.P1, P1, sizeof(cams.P1)); std::memcpy(cams.P2, P2, sizeof(cams.P2));
-    hipLaunchKernelGGL(k_triangulate, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, cams, (long long)N, dx1, dx2, dX,
-                       err1 ? de : (double*)nullptr, err2 ? de + N : (double*)nullptr);
-    MVUS_HIP(hipGetLastError());
-    MVUS_HIP(hipMemcpyAsync(X, dX, 2 * b2, hipMemcpyDeviceToHost, st));
-    if (err1) MVUS_HIP(hipMemcpyAsync(err1, de, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    if (err2) MVUS_HIP(hipMemcpyAsync(err2, de + N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    MVUS_HIP(hipStreamSynchronize(st));
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    cleanup();
-    return e.code;
-  } catch (const std::exception& e) {          // nothing throws across the ABI
-    g_create_error = e.what();
-    cleanup();
-    return MVUS_E_INVALID;
-  }
-  cleanup();
-  return MVUS_OK;
-}
-
-int mvus_spline_eval(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
-                     const double* coefs, int64_t nt, const double* t, double* X, int32_t* which) {
-  if (S < 1 || !interval || !knot_offsets || !knots || !coefs || nt < 0 || (nt > 0 && (!t || !X || !which))) { g_create_error = "spline_eval: bad arguments"; return MVUS_E_INVALID; }
-  for (int s = 0; s < S; ++s)
-    if (knot_offsets[s + 1] - knot_offsets[s] < 8) { g_create_error = "spline_eval: a cubic spline needs at least 8 knots"; return MVUS_E_INVALID; }
-  if (nt == 0) return MVUS_OK;
-  try {
-    CallBuffers cb;
-    cb.open(device);
-    std::vector<long long> koff(knot_offsets, knot_offsets + S + 1), coff(S + 1, 0);
-    for (int s = 0; s < S; ++s) coff[s + 1] = coff[s] + 3 * (koff[s + 1] - koff[s] - 4);
-    SplineSet sp;
-    sp.S = S;
-    sp.istart = cb.put(interval, (size_t)S); sp.iend = cb.put(interval + S, (size_t)S);
-    sp.knot_off = cb.put(koff.data(), koff.size()); sp.knots = cb.put(knots, (size_t)koff[S]);
-    sp.coef_off = cb.put(coff.data(), coff.size()); sp.coefs = cb.put(coefs, (size_t)coff[S]);
-    const double* dt = cb.put(t, (size_t)nt);
-    double* dX = cb.get<double>(3 * (size_t)nt);
-    int32_t* dw = cb.get<int32_t>((size_t)nt);
-    hipLaunchKernelGGL(k_spline_eval, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, cb.st, sp, (long long)nt, dt, dX, dw);
-    MVUS_HIP(hipGetLastError());
-    MVUS_HIP(hipMemcpyAsync(X, dX, sizeof(double) * 3 * nt, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipMemcpyAsync(which, dw, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {          // bad_alloc / length_error from the host-side tables: nothing throws across the ABI
-    g_create_error = e.what();
-    return MVUS_E_INVALID;
-  }
-  return MVUS_OK;
-}
-
-int mvus_spline_lsq(int32_t device, int32_t num_knots, const double* knots, int64_t m, const double* t, const double* X, double* coefs) {
-  const int n = num_knots - 4;
-  if (num_knots < 8 || !knots || m < 1 || !t || !X || !coefs) { g_create_error = "spline_lsq: bad arguments"; return MVUS_E_INVALID; }
-  for (int k = 1; k < num_knots; ++k) if (knots[k] < knots[k - 1]) { g_create_error = "spline_lsq: knot vector must be non-decreasing"; return MVUS_E_INVALID; }
-  for (int64_t i = 0; i < m; ++i) if (!(t[i] >= knots[3] && t[i] <= knots[n])) { g_create_error = "spline_lsq: data outside the knot interval"; return MVUS_E_INVALID; }
-  try {
-    CallBuffers cb;
-    cb.open(device);
-    const double* dk = cb.put(knots, (size_t)num_knots);
-    const double* dt = cb.put(t, (size_t)m);
-    const double* dX = cb.put(X, 3 * (size_t)m);
-    double* G = cb.get<double>(4 * (size_t)n);
-    double* rhs = cb.get<double>(3 * (size_t)n);
-    int* fail = cb.get<int>(1);
-    MVUS_HIP(hipMemsetAsync(G, 0, sizeof(double) * 4 * n, cb.st));
-    MVUS_HIP(hipMemsetAsync(rhs, 0, sizeof(double) * 3 * n, cb.st));
-    MVUS_HIP(hipMemsetAsync(fail, 0, sizeof(int), cb.st));
-    hipLaunchKernelGGL(k_lsq_accumulate, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, cb.st, dk, n, (long long)m, dt, dX, G, rhs);
-    hipLaunchKernelGGL(k_lsq_solve, dim3(1), dim3(64), 0, cb.st, n, G, rhs, fail);
-    MVUS_HIP(hipGetLastError());
-    int fh = 0;
-    MVUS_HIP(hipMemcpyAsync(coefs, rhs, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipMemcpyAsync(&fh, fail, sizeof(int), hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    if (fh) { g_create_error = "spline_lsq: the normal equations are not positive definite (a coefficient without data: Schoenberg-Whitney violated)"; return MVUS_E_NUMERIC; }
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {          // bad_alloc / length_error from the host-side tables: nothing throws across the ABI
-    g_create_error = e.what();
-    return MVUS_E_INVALID;
-  }
-  return MVUS_OK;
-}
-
-/* scipy.interpolate.splprep(X, u=u, s=s, k=3) on the GPU (spline_fit.hip.h): fppara's control flow here, every pass over the
- * samples and every banded solve on the device.  A SESSION holds the samples (checked and uploaded once) and the work arrays:
- * traj_to_spline's smooth_factor loop fits the same samples a dozen times with different s. */
-struct mvus_spline_fit {
-  CallBuffers cb;
-  int64_t m = 0;
-  std::vector<double> hu;                                  // the timestamps on the host (fpknot places knots at samples)
-  const double *du = nullptr, *dX = nullptr;
-  int32_t* span = nullptr;
-  double *q = nullptr, *term = nullptr, *tot_part = nullptr, *fp_part = nullptr;
-  int* fail = nullptr;
-  long long* first = nullptr;
-  double *cd = nullptr, *td = nullptr, *bd = nullptr, *out = nullptr;
-  FitWork<double> w1;
-  FitWork<dd> w2;
-  size_t cap = 0;
-};
-static int spline_fit_open_impl(mvus_spline_fit& S, int32_t device, int64_t m, const double* u, const double* X) {
-  constexpr int k = 3;
-  if (m <= k || m > (1ll << 30) || !u || !X) { g_create_error = "spline_smooth: bad arguments (m > 3 samples, s > 0)"; return MVUS_E_INVALID; }
-  for (int64_t i = 1; i < m; ++i) if (!(u[i] > u[i - 1])) { g_create_error = "spline_smooth: the timestamps must be strictly increasing"; return MVUS_E_INVALID; }
-  for (int64_t i = 0; i < 3 * m; ++i) if (!std::isfinite(X[i])) { g_create_error = "spline_smooth: non-finite sample"; return MVUS_E_INVALID; }
-  try {
-    S.m = m;
-    S.hu.assign(u, u + m);
-    CallBuffers& cb = S.cb;
-    cb.open(device);
-    S.du = cb.put(u, (size_t)m);
-    S.dX = cb.put(X, 3 * (size_t)m);
-    S.span = cb.get<int32_t>((size_t)m);
-    S.q = cb.get<double>(4 * (size_t)m);
-    S.term = cb.get<double>((size_t)m);
-    S.tot_part = cb.get<double>(1024);
-    S.fp_part = cb.get<double>(512 + kFitSliceBlocks);
-    S.fail = cb.get<int>(1);
-    MVUS_HIP(hipStreamSynchronize(cb.st));                 // u and X may go away after this call
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_create_error = e.what();
-    return MVUS_E_INVALID;
-  }
-  return MVUS_OK;
-}
-static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* t_out, double* c_out, double* fp_out, int32_t* ier_out) {
-  constexpr int k = 3, k1 = 4, k2 = 5, nmin = 8, maxit = 20;
-  constexpr double tol = 0.001;
-  const int64_t m = S.m;
-  const double* u = S.hu.data();
-  if (!n_out || !t_out || !c_out || !(s > 0.0) || !std::isfinite(s)) { g_create_error = "spline_smooth: bad arguments (m > 3 samples, s > 0)"; return MVUS_E_INVALID; }
-  const bool timing = std::getenv("MVUS_FIT_TIMING") != nullptr;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-  const auto t_begin = now();
-  int passes = 0;
-  const int nest = (int)m + 2 * k, nmax = (int)m + k1;
-  const auto t_checked = now();
-  auto t_ready = t_checked, t_fitted = t_checked;
-  try {
-    CallBuffers& cb = S.cb;
-    const double* du = S.du;
-    const double* dX = S.dX;
-    int32_t* span = S.span;
-    double* q = S.q;
-    double* term = S.term;
-    double* tot_part = S.tot_part;
-    double* fp_part = S.fp_part;
-    // Everything indexed by knots is sized by a CAPACITY that grows with the knot count (x4, up to FITPACK's nest = m + 6), not
-    // by nest: the trajectories traj_to_spline fits are 50x oversampled (560k samples for ~600 knots), and allocating and
-    // freeing ~40 arrays of nest doubles (430 MB with the double-double set) cost 70 of the 77 ms of such a fit
-    long long*& first = S.first;
-    double *&cd = S.cd, *&td = S.td, *&bd = S.bd, *&out = S.out;          // out: [0] sum diag(L), [1] f_p, [2] min diag(L), [3] max diag(L), [4..] residual per span
-    int* fail = S.fail;
-    FitWork<double>& w1 = S.w1;
-    FitWork<dd>& w2 = S.w2;
-    w1.penalty = false; w2.penalty = false;              // (the work arrays outlive a fit; what they hold does not)
-    bool precise = false;                                  // double-double from the first ill-conditioned pass on
-    bool diag_natural = true;                              // out[0] of the last least-squares pass is the sum FITPACK forms (see fit_band_solve)
-    int lsq_dd_n = -1;                                     // knot count whose normal equations w2 holds
-    MVUS_HIP(hipMemsetAsync(fail, 0, sizeof(int), cb.st));
-    std::vector<double> t, fpint, host, b;
-    std::vector<int> nrdata;
-    size_t& cap = S.cap;
-    auto ensure = [&](size_t need) {                      // between passes only: the device arrays hold nothing that outlives a pass
-      if (need <= cap || cap >= (size_t)nest) return;     // (nest = m + 6 knots is all FITPACK can ever ask for: nothing to grow to)
-      size_t c = std::max<size_t>(cap, 1024);
-      while (c < need) c *= 4;
-      cap = std::min<size_t>(c, (size_t)nest);
-      first = cb.get<long long>(cap + 1); cd = cb.get<double>(3 * cap); td = cb.get<double>(cap); bd = cb.get<double>(5 * cap);
-      out = cb.get<double>(cap + 4);
-      w1 = FitWork<double>(); w2 = FitWork<dd>(); lsq_dd_n = -1;
-      w1.alloc(cb, cap);
-      if (t.size() < cap) { t.resize(cap, 0.0); fpint.resize(cap, 0.0); nrdata.resize(cap, 0); }
-      if (host.size() < cap + 4) host.resize(cap + 4, 0.0);
-    };
-    ensure(nmin + 16);
-    if (t.size() < cap) { t.resize(cap, 0.0); fpint.resize(cap, 0.0); nrdata.resize(cap, 0); }      // (capacity kept from an earlier fit of this session)
-    if (host.size() < cap + 4) host.resize(cap + 4, 0.0);
-    if (timing) { MVUS_HIP(hipStreamSynchronize(cb.st)); t_ready = now(); }
-    const double ub = u[0], ue = u[m - 1], acc = tol * s;
-    int n = nmin, nplus = 0, ier = 0, nrint = 1, failed = 0;
-    double fpold = 0.0, fp0 = 0.0, fp = 0.0, p = -1.0;
-    nrdata[0] = (int)m - 2;
-    auto blocks = fit_blocks;
-    auto residual = [&](int ncoef, bool spans, int nspan) {            // c -> f_p (and the per-span residuals), fetched
-      hipLaunchKernelGGL(k_fit_residual, blocks(m), dim3(256), 0, cb.st, (long long)m, ncoef, span, q, dX, cd, term);
-      if (m > 8192) {                                                 // two stages (still one fixed order)
-        const int nbt = (int)std::min<long long>(1024, (m + 2047) / 2048);
-        hipLaunchKernelGGL(k_fit_total_partial, dim3(nbt), dim3(256), 0, cb.st, (long long)m, term, tot_part);
-        hipLaunchKernelGGL(k_fit_total, dim3(1), dim3(256), 0, cb.st, (long long)nbt, tot_part, out + 1);
-      } else {
-        hipLaunchKernelGGL(k_fit_total, dim3(1), dim3(256), 0, cb.st, (long long)m, term, out + 1);
-      }
-      if (spans) {
-        const int nslice = fit_slices(nspan);
-        hipLaunchKernelGGL(k_fit_fpint, dim3(nspan, nslice), dim3(256), 0, cb.st, nspan, first, term, out + 4, fp_part);
-        if (nslice > 1) hipLaunchKernelGGL(k_fit_fpint_final, blocks(nspan), dim3(256), 0, cb.st, nspan, nslice, first, term, fp_part, out + 4);
-      }
-      MVUS_HIP(hipGetLastError());
-      MVUS_HIP(hipMemcpyAsync(host.data(), out, sizeof(double) * (4 + (spans ? nspan : 0)), hipMemcpyDeviceToHost, cb.st));
-      MVUS_HIP(hipMemcpyAsync(&failed, fail, sizeof(int), hipMemcpyDeviceToHost, cb.st));
-      MVUS_HIP(hipStreamSynchronize(cb.st));
-    };
-    // a pass in fp64; when its Cholesky breaks down or the factor's diagonal spans more than four decades (cond(A^T A) >= 1e8)
-    // the pass is repeated in double-double, and so is every later pass of this call
-    auto ill = [&] { return failed != 0 || !(host[3] <= 1e4 * host[2]); };
-    auto solve = [&](int ncoef, int nrint_, int n8, bool smoothing, double pinv) {
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        if (!precise) {
-          if (!smoothing) diag_natural = fit_lsq_pass<double>(cb.st, w1, (long long)m, first, q, dX, ncoef, nrint_, cd, out, fail);
-          else fit_smooth_pass<double>(cb.st, w1, ncoef, n8, bd, pinv, cd, out, fail);
-        } else {
-          w2.alloc(cb, cap);
-          if (lsq_dd_n != n) { diag_natural = fit_lsq_pass<dd>(cb.st, w2, (long long)m, first, q, dX, ncoef, nrint_, cd, out, fail); lsq_dd_n = n; }
-          if (smoothing) fit_smooth_pass<dd>(cb.st, w2, ncoef, n8, bd, pinv, cd, out, fail);
-        }
-        residual(ncoef, !smoothing, nrint_);
-        ++passes;
-        if (std::getenv("MVUS_DEBUG")) std::fprintf(stderr, "spline_smooth: n=%d %s %s  diag(L) %.3e..%.3e  fp %.6e  fail %d\n", n, smoothing ? "smooth" : "lsq",
-                                                    precise ? "dd" : "fp64", host[2], host[3], host[1], failed);
-        if (precise) {                                    // floored pivots are accepted here (see k_band_solve)
-          if (!std::isfinite(host[1])) throw HipError{"spline_smooth: a banded system is not positive definite", MVUS_E_NUMERIC};
-          MVUS_HIP(hipMemsetAsync(fail, 0, sizeof(int), cb.st));
-          return;
-        }
-        if (!ill()) return;
-        precise = true;
-        MVUS_HIP(hipMemsetAsync(fail, 0, sizeof(int), cb.st));
-      }
-    };
-    int ncoef = 0;
-    for (;;) {                                             // fppara: do 200 iter = 1, m
-      ensure((size_t)n + 16);
-      if (n == nmin) ier = -2;
-      nrint = n - nmin + 1;
-      ncoef = n - k1;
-      for (int j = 0; j < k1; ++j) { t[j] = ub; t[n - 1 - j] = ue; }
-      MVUS_HIP(hipMemcpyAsync(td, t.data(), sizeof(double) * n, hipMemcpyHostToDevice, cb.st));
-      MVUS_HIP(hipStreamSynchronize(cb.st));               // t is modified on the host below
-      hipLaunchKernelGGL(k_fit_basis, blocks(m), dim3(256), 0, cb.st, (long long)m, du, td, ncoef, span, q);
-      hipLaunchKernelGGL(k_fit_first, blocks(nrint + 1), dim3(256), 0, cb.st, (long long)m, du, td, nrint, first);
-      solve(ncoef, nrint, 0, false, 0.0);
-      fp = host[1];
-      if (ier == -2) fp0 = fp;
-      double fpms = fp - s;
-      if (std::fabs(fpms) < acc) break;
-      if (fpms < 0.0) {
-        if (ier == -2) break;                              // the least-squares polynomial is acceptable
-        // ---- part 2: the smoothing spline, F(p) = s ----
-        fitpack::fpdisc(t, n, b);
-        const int n8 = n - nmin;
-        MVUS_HIP(hipMemcpyAsync(bd, b.data(), sizeof(double) * b.size(), hipMemcpyHostToDevice, cb.st));
-        double p1 = 0.0, f1 = fp0 - s, p3 = -1.0, f3 = fpms;
-        if (!diag_natural) {                               // the pass above was partitioned: one chain over the same normal equations for sum a(i,1)
-          if (precise) fit_lsq_diag<dd>(cb.st, w2, ncoef, out); else fit_lsq_diag<double>(cb.st, w1, ncoef, out);
-          MVUS_HIP(hipGetLastError());
-          MVUS_HIP(hipMemcpyAsync(host.data(), out, sizeof(double), hipMemcpyDeviceToHost, cb.st));
-          MVUS_HIP(hipStreamSynchronize(cb.st));
-        }
-        p = (double)ncoef / host[0];
-        int ich1 = 0, ich3 = 0;
-        for (int iter = 1; iter <= maxit; ++iter) {
-          solve(ncoef, nrint, n8, true, 1.0 / p);
-          fp = host[1];
-          fpms = fp - s;
-          if (std::fabs(fpms) < acc) break;
-          if (iter == maxit) { ier = 3; break; }
-          const double p2 = p, f2 = fpms;
-          if (ich3 == 0) {
-            if (f2 - f3 <= acc) {                          // the initial choice of p is too large
-              p3 = p2; f3 = f2;
-              p = p * 0.04;
-              if (p <= p1) p = p1 * 0.9 + p2 * 0.1;
-              continue;
-            }
-            if (f2 < 0.0) ich3 = 1;
-          }
-          if (ich1 == 0) {
-            if (f1 - f2 <= acc) {                          // the initial choice of p is too small
-              p1 = p2; f1 = f2;
-              p = p / 0.04;
-              if (p3 < 0.0) continue;
-              if (p >= p3) p = p2 * 0.1 + p3 * 0.9;
-              continue;
-            }
-            if (f2 > 0.0) ich1 = 1;
-          }
-          if (f2 >= f1 || f2 <= f3) { ier = 2; break; }
-          p = fitpack::fprati(p1, f1, p2, f2, p3, f3);
-        }
-        if (ier < 0) ier = 0;
-        break;
-      }
-      if (n == nmax) { ier = -1; break; }
-      if (n == nest) { ier = 1; break; }
-      // ---- more knots ----
-      if (ier == 0) {
-        int npl1 = nplus * 2;
-        const double rn = nplus;
-        if (fpold - fp > acc) npl1 = (int)(rn * fpms / (fpold - fp));
-        nplus = std::min(nplus * 2, std::max(std::max(npl1, nplus / 2), 1));
-      } else {
-        nplus = 1;
-        ier = 0;
-      }
-      fpold = fp;
-      {                                                    // room for the knots about to be added (host arrays; the device side follows at the top of the loop)
-        const size_t need = std::min<size_t>((size_t)nest, (size_t)n + (size_t)nplus + 16);
-        if (need > t.size()) { t.resize(need, 0.0); fpint.resize(need, 0.0); nrdata.resize(need, 0); }
-      }
-      for (int j = 0; j < nrint; ++j) fpint[j] = host[4 + j];
-      fitpack::fpknot_batch(u, t, n, fpint, nrdata, nrint, nplus, nmax, nest);
-      if (n == nmax) {                                      // fppara label 10: the knots of the interpolating spline
-        if (t.size() < (size_t)nest) { t.resize((size_t)nest, 0.0); fpint.resize((size_t)nest, 0.0); nrdata.resize((size_t)nest, 0); }
-        int i = k2, j = k / 2 + 2;
-        for (int l = 0; l < (int)m - k1; ++l) { t[i - 1] = u[j - 1]; ++i; ++j; }
-      }
-    }
-    t_fitted = now();
-    std::vector<double> ch(3 * (size_t)ncoef);
-    MVUS_HIP(hipMemcpyAsync(ch.data(), cd, sizeof(double) * 3 * ncoef, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    for (int d = 0; d < 3; ++d) for (int j = 0; j < ncoef; ++j) c_out[(size_t)d * nest + j] = ch[(size_t)d * ncoef + j];
-    for (int j = 0; j < n; ++j) t_out[j] = t[j];
-    *n_out = n;
-    if (fp_out) *fp_out = fp;
-    if (ier_out) *ier_out = ier;
-    if (timing) std::fprintf(stderr, "spline_smooth: m=%lld n=%d passes=%d | input checks %.2f ms, buffers+upload %.2f ms, passes %.2f ms", (long long)m, n, passes,
-                             ms(t_begin, t_checked), ms(t_checked, t_ready), ms(t_ready, t_fitted));
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {          // bad_alloc / length_error on absurd sizes must not cross the C ABI
-    g_create_error = e.what();
-    return MVUS_E_INVALID;
-  }
-  if (timing) std::fprintf(stderr, ", total %.2f ms\n", ms(t_begin, now()));
-  return MVUS_OK;
-}
-
-int mvus_spline_fit_open(int32_t device, int64_t m, const double* u, const double* X, mvus_spline_fit** out) {
-  if (!out) { g_create_error = "spline_fit_open: bad arguments"; return MVUS_E_INVALID; }
-  *out = nullptr;
-  mvus_spline_fit* S = nullptr;
-  try { S = new mvus_spline_fit(); } catch (const std::exception& e) { g_create_error = e.what(); return MVUS_E_INVALID; }
-  const int rc = spline_fit_open_impl(*S, device, m, u, X);
-  if (rc != MVUS_OK) { delete S; return rc; }
-  *out = S;
-  return MVUS_OK;
-}
-int mvus_spline_fit_smooth(mvus_spline_fit* S, double s, int32_t* n_out, double* t_out, double* c_out, double* fp_out, int32_t* ier_out) {
-  if (!S) { g_create_error = "spline_fit_smooth: no session"; return MVUS_E_INVALID; }
-  return spline_fit_run(*S, s, n_out, t_out, c_out, fp_out, ier_out);
-}
-void mvus_spline_fit_close(mvus_spline_fit* S) { delete S; }
-
-int mvus_spline_smooth(int32_t device, int64_t m, const double* u, const double* X, double s, int32_t* n_out, double* t_out, double* c_out,
-                       double* fp_out, int32_t* ier_out) {
-  if (!n_out || !t_out || !c_out || !(s > 0.0) || !std::isfinite(s)) { g_create_error = "spline_smooth: bad arguments (m > 3 samples, s > 0)"; return MVUS_E_INVALID; }
-  mvus_spline_fit S;
-  const int rc = spline_fit_open_impl(S, device, m, u, X);
-  if (rc != MVUS_OK) return rc;
-  return spline_fit_run(S, s, n_out, t_out, c_out, fp_out, ier_out);
-}
-
-/* cv2.solvePnPRansac(objectPoints, imagePoints, K, d, reprojectionError) as Scene.get_camera_pose calls it (pnp.hip.h) */
-int mvus_pnp_ransac(int32_t device, int64_t N, const double* X, const double* uv, const double* K, const double* d, double reproj_error,
-                    int32_t iterations, uint64_t seed, double* rvec, double* tvec, uint8_t* inliers, int64_t* n_inliers) {
-  if (N < 6 || N > (1ll << 30) || !X || !uv || !K || !d || !rvec || !tvec || !(reproj_error > 0.0) || iterations < 1 || iterations > 65536) {
-    g_create_error = "pnp_ransac: bad arguments (at least 6 points, reprojection error > 0, 1..65536 iterations)";
-    return MVUS_E_INVALID;
-  }
-  for (int64_t i = 0; i < 3 * N; ++i) if (!std::isfinite(X[i])) { g_create_error = "pnp_ransac: non-finite object point"; return MVUS_E_INVALID; }
-  for (int64_t i = 0; i < 2 * N; ++i) if (!std::isfinite(uv[i])) { g_create_error = "pnp_ransac: non-finite image point"; return MVUS_E_INVALID; }
-  // the object points are centred and scaled (the direct linear transform is badly conditioned otherwise); a pose (R, t')
-  // of the scaled points is the pose (R, sigma t' - R m) of the original ones
-  try {
-  double m[3] = {0.0, 0.0, 0.0}, sigma = 0.0;
-  for (int a = 0; a < 3; ++a) { for (int64_t i = 0; i < N; ++i) m[a] += X[a * N + i]; m[a] /= (double)N; }
-  for (int a = 0; a < 3; ++a) for (int64_t i = 0; i < N; ++i) sigma += (X[a * N + i] - m[a]) * (X[a * N + i] - m[a]);
-  sigma = std::sqrt(sigma / (3.0 * (double)N));
-  if (!(sigma > 0.0)) { g_create_error = "pnp_ransac: all object points coincide"; return MVUS_E_INVALID; }
-  std::vector<double> Xc(3 * (size_t)N);
-  for (int a = 0; a < 3; ++a) for (int64_t i = 0; i < N; ++i) Xc[a * N + i] = (X[a * N + i] - m[a]) / sigma;
-  double Kd[9] = {K[0], K[1], K[2], K[3], d[0], d[1], d[2], d[3], d[4]};
-  {
-    CallBuffers cb;
-    cb.open(device);
-    const double* dX = cb.put(Xc.data(), Xc.size());
-    const double* duv = cb.put(uv, 2 * (size_t)N);
-    const double* dK = cb.put(Kd, 9);
-    double* xn = cb.get<double>(2 * (size_t)N);
-    double* poses = cb.get<double>(13 * (size_t)iterations);
-    int32_t* counts = cb.get<int32_t>((size_t)iterations);
-    uint8_t* mask = cb.get<uint8_t>((size_t)N);
-    double* pose_d = cb.get<double>(13);
-    double* acc_d = cb.get<double>(29);
-    const double thr2 = reproj_error * reproj_error;
-    hipLaunchKernelGGL(k_pnp_normalise, fit_blocks(N), dim3(256), 0, cb.st, (long long)N, duv, dK, xn);
-    hipLaunchKernelGGL(k_pnp_hypotheses, dim3((iterations + 63) / 64), dim3(64), 0, cb.st, iterations, (unsigned long long)seed, (long long)N, dX, xn, poses);
-    hipLaunchKernelGGL(k_pnp_score, dim3(iterations), dim3(256), 0, cb.st, (long long)N, dX, duv, dK, poses, thr2, counts);
-    MVUS_HIP(hipGetLastError());
-    std::vector<int32_t> cnt((size_t)iterations);
-    MVUS_HIP(hipMemcpyAsync(cnt.data(), counts, sizeof(int32_t) * iterations, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    int best = 0;
-    for (int h = 1; h < iterations; ++h) if (cnt[h] > cnt[best]) best = h;          // ties: the first hypothesis
-    if (cnt[best] < 6) { g_create_error = "pnp_ransac: no hypothesis is supported by six points (reprojection error too small, or no consistent pose)"; return MVUS_E_NUMERIC; }
-    double pose[13];
-    MVUS_HIP(hipMemcpyAsync(pose, poses + 13ll * best, sizeof(double) * 13, hipMemcpyDeviceToHost, cb.st));
-    hipLaunchKernelGGL(k_pnp_mask, fit_blocks(N), dim3(256), 0, cb.st, (long long)N, dX, duv, dK, poses + 13ll * best, thr2, mask);
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    // damped Gauss-Newton on the inliers; the normal equations come from the device, the 6x6 solve is done here
-    double acc[29], cand[13], acc2[29];
-    auto evaluate = [&](const double* ps, double* out) {
-      MVUS_HIP(hipMemcpyAsync(pose_d, ps, sizeof(double) * 13, hipMemcpyHostToDevice, cb.st));
-      hipLaunchKernelGGL(k_pnp_normal, dim3(1), dim3(256), 0, cb.st, (long long)N, dX, duv, dK, pose_d, mask, acc_d);
-      MVUS_HIP(hipMemcpyAsync(out, acc_d, sizeof(double) * 29, hipMemcpyDeviceToHost, cb.st));
-      MVUS_HIP(hipStreamSynchronize(cb.st));
-    };
-    evaluate(pose, acc);
-    double lambda = 1e-3;
-    for (int it = 0; it < 100; ++it) {
-      double Hm[6][6], g[6], L[6][6], dlt[6];
-      int e = 0;
-      for (int a = 0; a < 6; ++a) for (int b = 0; b <= a; ++b) { Hm[a][b] = Hm[b][a] = acc[e++]; }
-      for (int a = 0; a < 6; ++a) { g[a] = acc[21 + a]; Hm[a][a] += lambda * (Hm[a][a] > 0.0 ? Hm[a][a] : 1.0); }
-      bool pd = true;
-      for (int j = 0; j < 6 && pd; ++j) {
-        double s = Hm[j][j];
-        for (int k2 = 0; k2 < j; ++k2) s -= L[j][k2] * L[j][k2];
-        if (!(s > 0.0)) { pd = false; break; }
-        L[j][j] = std::sqrt(s);
-        for (int i = j + 1; i < 6; ++i) { double v = Hm[i][j]; for (int k2 = 0; k2 < j; ++k2) v -= L[i][k2] * L[j][k2]; L[i][j] = v / L[j][j]; }
-      }
-      if (!pd) { lambda *= 10.0; if (lambda > 1e10) break; continue; }
-      for (int i = 0; i < 6; ++i) { double v = -g[i]; for (int k2 = 0; k2 < i; ++k2) v -= L[i][k2] * dlt[k2]; dlt[i] = v / L[i][i]; }
-      for (int i = 5; i >= 0; --i) { double v = dlt[i]; for (int k2 = i + 1; k2 < 6; ++k2) v -= L[k2][i] * dlt[k2]; dlt[i] = v / L[i][i]; }
-      double dR[9], W[9];
-      rodrigues(dlt, dR, W);
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) cand[3 * a + b] = dR[3 * a] * pose[b] + dR[3 * a + 1] * pose[3 + b] + dR[3 * a + 2] * pose[6 + b];
-      for (int a = 0; a < 3; ++a) cand[9 + a] = pose[9 + a] + dlt[3 + a];
-      cand[12] = 1.0;
-      evaluate(cand, acc2);
-      double step = 0.0;
-      for (int a = 0; a < 6; ++a) step = std::max(step, std::fabs(dlt[a]));
-      if (acc2[28] == 0.0 && acc2[27] <= acc[27]) {
-        const double gain = acc[27] - acc2[27];
-        std::memcpy(pose, cand, sizeof(pose));
-        std::memcpy(acc, acc2, sizeof(acc));
-        lambda = std::max(lambda * 0.1, 1e-12);
-        if (step < 1e-13 || gain <= 1e-15 * acc[27]) break;
-      } else {
-        lambda *= 10.0;
-        if (lambda > 1e10 || step < 1e-14) break;
-      }
-    }
-    // back to the scale of the original points
-    for (int a = 0; a < 3; ++a) tvec[a] = sigma * pose[9 + a] - (pose[3 * a] * m[0] + pose[3 * a + 1] * m[1] + pose[3 * a + 2] * m[2]);
-    rotation_to_rvec(pose, rvec);
-    if (inliers) MVUS_HIP(hipMemcpyAsync(inliers, mask, (size_t)N, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    if (n_inliers) *n_inliers = cnt[best];
-  }
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    return MVUS_E_HIP;
-  } catch (const std::exception& e) {
-    g_create_error = e.what();
-    return MVUS_E_INVALID;
-  }
-  return MVUS_OK;
-}
-
-}  // extern "C"
-
-// ---- two-view geometry (epipolar.hip.h): host halves ------------------------------------------------------------------------
-namespace {
-// eigen-decomposition of a symmetric n x n matrix (row-major, destroyed) by cyclic Jacobi rotations: w[n] ascending, V columns
-void sym_eig_jacobi(int n, double* A, double* w, double* V) {
-  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) V[i * n + j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0.0, tot = 0.0;
-    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { tot += A[i * n + j] * A[i * n + j]; if (i != j) off += A[i * n + j] * A[i * n + j]; }
-    if (!(off > 1e-30 * tot)) break;
-    for (int p = 0; p < n - 1; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        const double apq = A[p * n + q];
-        if (apq == 0.0) continue;
-        const double th = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
-        const double t = (th >= 0.0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(1.0 + th * th));
-        const double c = 1.0 / std::sqrt(1.0 + t * t), s = t * c;
-        for (int k = 0; k < n; ++k) {                       // A <- J^T A J
-          const double akp = A[k * n + p], akq = A[k * n + q];
-          A[k * n + p] = c * akp - s * akq; A[k * n + q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < n; ++k) {
-          const double apk = A[p * n + k], aqk = A[q * n + k];
-          A[p * n + k] = c * apk - s * aqk; A[q * n + k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < n; ++k) {
-          const double vkp = V[k * n + p], vkq = V[k * n + q];
-          V[k * n + p] = c * vkp - s * vkq; V[k * n + q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  std::vector<int> ord(n);
-  for (int i = 0; i < n; ++i) ord[i] = i;
-  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return A[a * n + a] < A[b * n + b]; });
-  std::vector<double> Vs((size_t)n * n);
-  for (int k = 0; k < n; ++k) { w[k] = A[ord[k] * n + ord[k]]; for (int i = 0; i < n; ++i) Vs[i * n + k] = V[i * n + ord[k]]; }
-  std::memcpy(V, Vs.data(), sizeof(double) * n * n);
-}
-
-// unit right null vector of a 3x3 matrix M (smallest eigenvector of M^T M); left: of M^T
-void null3(const double* M, bool left, double* e) {
-  double A[9], w[3], V[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double s = 0.0;
-      for (int k = 0; k < 3; ++k) s += left ? M[3 * i + k] * M[3 * j + k] : M[3 * k + i] * M[3 * k + j];
-      A[3 * i + j] = s;
-    }
-  sym_eig_jacobi(3, A, w, V);
-  for (int i = 0; i < 3; ++i) e[i] = V[3 * i];
-}
-
-// unit null vector of a rank-2 3x3 matrix as the largest cross product of two of its rows (right) or columns (left): exact to
-// rounding for a rank-2 matrix, where an eigenvector of M^T M carries the error of squaring it
-void null3_cross(const double* M, bool left, double* e) {
-  auto vec = [&](int k, double* v) { for (int a = 0; a < 3; ++a) v[a] = left ? M[3 * a + k] : M[3 * k + a]; };
-  double best = -1.0;
-  for (int i = 0; i < 2; ++i)
-    for (int j = i + 1; j < 3; ++j) {
-      double a[3], b[3], c[3];
-      vec(i, a); vec(j, b);
-      c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-      const double n = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-      if (n > best) { best = n; for (int k = 0; k < 3; ++k) e[k] = c[k]; }
-    }
-  const double n = std::sqrt(best);
-  if (n > 0.0) for (int k = 0; k < 3; ++k) e[k] /= n;
-  else null3(M, left, e);
-}
-
-// F (normalised coordinates, from the 8-point normal matrix) -> rank 2: F (I - v v^T) with v the right null vector of F
-void rank2(double* F) {
-  double v[3];
-  null3(F, false, v);
-  double Fv[3];
-  for (int i = 0; i < 3; ++i) Fv[i] = F[3 * i] * v[0] + F[3 * i + 1] * v[1] + F[3 * i + 2] * v[2];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) F[3 * i + j] -= Fv[i] * v[j];
-}
-
-double det3h(const double* A) { return A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]); }
-void mul3(const double* A, const double* B, double* C) {
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
-
-// compute_Rt_from_E (epipolar.py:513-539): E = U S Vh; Vh <- -Vh when det(U Vh) < 0; R1 = U W Vh, R2 = U W^T Vh (each times its
-// determinant), t = +-U[:, 2]; candidates (R1, t), (R1, -t), (R2, t), (R2, -t) as 3x4 row-major
-void essential_candidates(const double* E, double (*P)[12]) {
-  double A[9], w[3], V[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) { double s = 0.0; for (int k = 0; k < 3; ++k) s += E[3 * k + i] * E[3 * k + j]; A[3 * i + j] = s; }
-  sym_eig_jacobi(3, A, w, V);                          // ascending: columns 2, 1 are the two large singular directions
-  double v[3][3], u[3][3];
-  for (int i = 0; i < 3; ++i) { v[0][i] = V[3 * i + 2]; v[1][i] = V[3 * i + 1]; v[2][i] = V[3 * i]; }
-  for (int k = 0; k < 2; ++k) {
-    double n = 0.0;
-    for (int i = 0; i < 3; ++i) { u[k][i] = E[3 * i] * v[k][0] + E[3 * i + 1] * v[k][1] + E[3 * i + 2] * v[k][2]; }
-    if (k == 1) { double d = 0.0; for (int i = 0; i < 3; ++i) d += u[1][i] * u[0][i]; for (int i = 0; i < 3; ++i) u[1][i] -= d * u[0][i]; }
-    for (int i = 0; i < 3; ++i) n += u[k][i] * u[k][i];
-    n = std::sqrt(n);
-    for (int i = 0; i < 3; ++i) u[k][i] /= n;
-  }
-  u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1];
-  u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2];
-  u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
-  double U[9], Vh[9];
-  for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) { U[3 * i + k] = u[k][i]; Vh[3 * k + i] = v[k][i]; }
-  double UV[9];
-  mul3(U, Vh, UV);
-  if (det3h(UV) < 0.0) for (int a = 0; a < 9; ++a) Vh[a] = -Vh[a];
-  const double W[9] = {0.0, -1.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0}, Wt[9] = {0.0, 1.0, 0.0, -1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-  double T[9], R1[9], R2[9];
-  mul3(U, W, T); mul3(T, Vh, R1);
-  mul3(U, Wt, T); mul3(T, Vh, R2);
-  const double d1 = det3h(R1), d2 = det3h(R2);
-  for (int a = 0; a < 9; ++a) { R1[a] *= d1; R2[a] *= d2; }
-  const double* Rs[4] = {R1, R1, R2, R2};
-  for (int c = 0; c < 4; ++c) {
-    const double sg = (c & 1) ? -1.0 : 1.0;
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) P[c][4 * i + j] = Rs[c][3 * i + j];
-      P[c][4 * i + 3] = sg * U[3 * i + 2];
-    }
-  }
-}
-
-int epi_fail(const char* msg, int code) { g_create_error = msg; return code; }
-}  // namespace
-
-extern "C" {
-
-int mvus_fundamental_ransac(int32_t device, int32_t P, const int64_t* offsets, const double* x1, const double* x2, double thresh,
-                            int32_t iterations, uint64_t seed, double* F_out, uint8_t* mask, int32_t* n_inliers) {
-  if (P < 1 || !offsets || !x1 || !x2 || !F_out || !mask || !(thresh > 0.0) || !std::isfinite(thresh) || iterations < 1 || iterations > 65536)
-    return epi_fail("fundamental_ransac: bad arguments (P >= 1, thresh > 0, 1..65536 iterations)", MVUS_E_INVALID);
-  if (offsets[0] != 0) return epi_fail("fundamental_ransac: offsets[0] must be 0", MVUS_E_INVALID);
-  for (int p = 0; p < P; ++p)
-    if (offsets[p + 1] - offsets[p] < 8) return epi_fail("fundamental_ransac: every problem needs at least 8 pairs", MVUS_E_INVALID);
-  const int64_t Ntot = offsets[P];
-  if (Ntot > (1ll << 31)) return epi_fail("fundamental_ransac: more than 2^31 pairs", MVUS_E_INVALID);
-  for (int64_t i = 0; i < 2 * Ntot; ++i)
-    if (!std::isfinite(x1[i]) || !std::isfinite(x2[i])) return epi_fail("fundamental_ransac: non-finite point", MVUS_E_INVALID);
-  const int H = iterations, M = kFmSlots * H, B = kFmRefitBlocks;
-  const double thr2 = thresh * thresh;
-  try {
-    CallBuffers cb;
-    cb.open(device);
-    const long long* doffs = reinterpret_cast<const long long*>(cb.put(offsets, (size_t)P + 1));
-    const double* dx1 = cb.put(x1, 2 * (size_t)Ntot);
-    const double* dx2 = cb.put(x2, 2 * (size_t)Ntot);
-    double* norm = cb.get<double>(6 * (size_t)P);
-    double* models = cb.get<double>((size_t)P * M * kFmModel);
-    int32_t* counts = cb.get<int32_t>((size_t)P * M);
-    double* dF = cb.get<double>(9 * (size_t)P);
-    uint8_t* mwin = cb.get<uint8_t>((size_t)Ntot);
-    uint8_t* mref = cb.get<uint8_t>((size_t)Ntot);
-    double* parts = cb.get<double>((size_t)P * B * 45);
-    int32_t* rcnt = cb.get<int32_t>((size_t)P * B);
-    hipLaunchKernelGGL(k_fm_normalise, dim3(P), dim3(256), 0, cb.st, doffs, (long long)Ntot, dx1, dx2, norm);
-    hipLaunchKernelGGL(k_fm_hypotheses, dim3((H + 63) / 64, P), dim3(64), 0, cb.st, H, (unsigned long long)seed, doffs, (long long)Ntot, dx1, dx2, norm, models);
-    hipLaunchKernelGGL(k_fm_score, dim3((M + 255) / 256, P), dim3(256), 0, cb.st, H, doffs, (long long)Ntot, dx1, dx2, models, thr2, counts);
-    MVUS_HIP(hipGetLastError());
-    std::vector<int32_t> cnt((size_t)P * M);
-    std::vector<double> nrm(6 * (size_t)P);
-    MVUS_HIP(hipMemcpyAsync(cnt.data(), counts, sizeof(int32_t) * cnt.size(), hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipMemcpyAsync(nrm.data(), norm, sizeof(double) * nrm.size(), hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    // the winner of every problem: highest count, lowest model index on ties
-    std::vector<double> Fw(9 * (size_t)P), Fr(9 * (size_t)P);
-    std::vector<int32_t> best_cnt(P);
-    for (int p = 0; p < P; ++p) {
-      const int32_t* c = cnt.data() + (size_t)p * M;
-      int best = 0;
-      for (int m = 1; m < M; ++m) if (c[m] > c[best]) best = m;
-      if (c[best] < 0) return epi_fail("fundamental_ransac: no valid 7-point model (degenerate configuration)", MVUS_E_NUMERIC);
-      best_cnt[p] = c[best];
-      MVUS_HIP(hipMemcpyAsync(Fw.data() + 9 * (size_t)p, models + ((size_t)p * M + best) * kFmModel, sizeof(double) * 9, hipMemcpyDeviceToHost, cb.st));
-    }
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    MVUS_HIP(hipMemcpyAsync(dF, Fw.data(), sizeof(double) * 9 * P, hipMemcpyHostToDevice, cb.st));
-    hipLaunchKernelGGL(k_fm_refit, dim3(B, P), dim3(256), 0, cb.st, doffs, (long long)Ntot, dx1, dx2, norm, dF, thr2, mwin, parts);
-    MVUS_HIP(hipGetLastError());
-    std::vector<double> hp((size_t)P * B * 45);
-    MVUS_HIP(hipMemcpyAsync(hp.data(), parts, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    // normalised 8-point refit on the winner's inliers: smallest eigenvector of the normal matrix, rank 2, denormalised
-    std::vector<char> have_refit(P, 0);
-    for (int p = 0; p < P; ++p) {
-      double Mx[81], w[9], V[81], Fn[9];
-      double up[45];
-      for (int e = 0; e < 45; ++e) { double s = 0.0; for (int b = 0; b < B; ++b) s += hp[((size_t)p * B + b) * 45 + e]; up[e] = s; }
-      int e = 0;
-      for (int a = 0; a < 9; ++a) for (int b = a; b < 9; ++b) { Mx[9 * a + b] = Mx[9 * b + a] = up[e++]; }
-      if (best_cnt[p] < 8) { std::memcpy(Fr.data() + 9 * (size_t)p, Fw.data() + 9 * (size_t)p, sizeof(double) * 9); continue; }
-      sym_eig_jacobi(9, Mx, w, V);
-      for (int a = 0; a < 9; ++a) Fn[a] = V[9 * a];
-      rank2(Fn);
-      double Fd[9];
-      fm_denormalise(Fn, nrm.data() + 6 * (size_t)p, Fd);
-      bool ok = true;
-      for (int a = 0; a < 9; ++a) ok = ok && std::isfinite(Fd[a]);
-      std::memcpy(Fr.data() + 9 * (size_t)p, ok ? Fd : Fw.data() + 9 * (size_t)p, sizeof(double) * 9);
-      have_refit[p] = ok ? 1 : 0;
-    }
-    MVUS_HIP(hipMemcpyAsync(dF, Fr.data(), sizeof(double) * 9 * P, hipMemcpyHostToDevice, cb.st));
-    hipLaunchKernelGGL(k_fm_mask, dim3(B, P), dim3(256), 0, cb.st, doffs, (long long)Ntot, dx1, dx2, dF, thr2, mref, rcnt);
-    MVUS_HIP(hipGetLastError());
-    std::vector<int32_t> rc((size_t)P * B);
-    std::vector<uint8_t> hw((size_t)Ntot);
-    MVUS_HIP(hipMemcpyAsync(rc.data(), rcnt, sizeof(int32_t) * rc.size(), hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipMemcpyAsync(hw.data(), mwin, (size_t)Ntot, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipMemcpyAsync(mask, mref, (size_t)Ntot, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    for (int p = 0; p < P; ++p) {
-      int32_t c = 0;
-      for (int b = 0; b < B; ++b) c += rc[(size_t)p * B + b];
-      const bool refit = have_refit[p] && c >= best_cnt[p];
-      std::memcpy(F_out + 9 * (size_t)p, (refit ? Fr : Fw).data() + 9 * (size_t)p, sizeof(double) * 9);
-      if (!refit) std::memcpy(mask + offsets[p], hw.data() + offsets[p], (size_t)(offsets[p + 1] - offsets[p]));
-      if (n_inliers) n_inliers[p] = refit ? c : best_cnt[p];
-    }
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    return MVUS_E_HIP;
-  } catch (const std::exception& e) {
-    g_create_error = e.what();
-    return MVUS_E_INVALID;
-  }
-  return MVUS_OK;
-}
-
-int mvus_correct_matches(int32_t device, int64_t N, const double* F, const double* x1, const double* x2, double* x1c, double* x2c) {
-  if (N < 0 || !F || (N > 0 && (!x1 || !x2 || !x1c || !x2c))) return epi_fail("correct_matches: bad arguments", MVUS_E_INVALID);
-  double nn = 0.0;
-  for (int a = 0; a < 9; ++a) { if (!std::isfinite(F[a])) return epi_fail("correct_matches: F is not finite", MVUS_E_INVALID); nn += F[a] * F[a]; }
-  if (!(nn > 0.0)) return epi_fail("correct_matches: F is zero", MVUS_E_INVALID);
-  if (N == 0) return MVUS_OK;
-  try {
-    EpiF f;
-    for (int a = 0; a < 9; ++a) f.F[a] = F[a] / std::sqrt(nn);
-    null3_cross(f.F, false, f.e1);
-    null3_cross(f.F, true, f.e2);
-    CallBuffers cb;
-    cb.open(device);
-    const double* dx1 = cb.put(x1, 2 * (size_t)N);
-    const double* dx2 = cb.put(x2, 2 * (size_t)N);
-    double* o1 = cb.get<double>(2 * (size_t)N);
-    double* o2 = cb.get<double>(2 * (size_t)N);
-    hipLaunchKernelGGL(k_correct_matches, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, cb.st, f, (long long)N, dx1, dx2, o1, o2);
-    MVUS_HIP(hipGetLastError());
-    MVUS_HIP(hipMemcpyAsync(x1c, o1, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipMemcpyAsync(x2c, o2, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    return MVUS_E_HIP;
-  } catch (const std::exception& e) {
-    g_create_error = e.what();
-    return MVUS_E_INVALID;
-  }
-  return MVUS_OK;
-}
-
-int mvus_pose_from_essential(int32_t device, int64_t N, const double* E, const double* x1n, const double* x2n, double* P2_out, double* X_out) {
-  if (N < 1 || N > (1ll << 31) || !E || !x1n || !x2n || !P2_out || !X_out) return epi_fail("pose_from_essential: bad arguments (N >= 1)", MVUS_E_INVALID);
-  for (int a = 0; a < 9; ++a) if (!std::isfinite(E[a])) return epi_fail("pose_from_essential: E is not finite", MVUS_E_INVALID);
-  for (int64_t i = 0; i < 2 * N; ++i)
-    if (!std::isfinite(x1n[i]) || !std::isfinite(x2n[i])) return epi_fail("pose_from_essential: non-finite point", MVUS_E_INVALID);
-  try {
-    EpiCand cand;
-    essential_candidates(E, cand.P2);
-    for (int c = 0; c < 4; ++c) for (int a = 0; a < 12; ++a)
-      if (!std::isfinite(cand.P2[c][a])) return epi_fail("pose_from_essential: E has no valid decomposition", MVUS_E_NUMERIC);
-    const int B = (int)std::min<long long>(64, (N + 255) / 256);
-    CallBuffers cb;
-    cb.open(device);
-    const double* dx1 = cb.put(x1n, 2 * (size_t)N);
-    const double* dx2 = cb.put(x2n, 2 * (size_t)N);
-    int32_t* dcnt = cb.get<int32_t>(4 * (size_t)B);
-    double* dX = cb.get<double>(4 * (size_t)N);
-    hipLaunchKernelGGL(k_cheirality4, dim3(B, 4), dim3(256), 0, cb.st, cand, (long long)N, dx1, dx2, dcnt);
-    MVUS_HIP(hipGetLastError());
-    std::vector<int32_t> hc(4 * (size_t)B);
-    MVUS_HIP(hipMemcpyAsync(hc.data(), dcnt, sizeof(int32_t) * hc.size(), hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    long long infront_max = 0;
-    int chosen = -1;
-    for (int c = 0; c < 4; ++c) {
-      long long s = 0;
-      for (int b = 0; b < B; ++b) s += hc[(size_t)c * B + b];
-      if (s > infront_max) { infront_max = s; chosen = c; }          // strict: the first candidate to exceed the running maximum
-    }
-    if (chosen < 0) return epi_fail("pose_from_essential: no candidate puts a point in front of a camera", MVUS_E_NUMERIC);
-    TriCams cams;
-    const double I34[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
-    std::memcpy(cams.P1, I34, sizeof(I34));
-    std::memcpy(cams.P2, cand.P2[chosen], sizeof(cams.P2));
-    hipLaunchKernelGGL(k_triangulate, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, cb.st, cams, (long long)N, dx1, dx2, dX,
-                       (double*)nullptr, (double*)nullptr);
-    MVUS_HIP(hipGetLastError());
-    MVUS_HIP(hipMemcpyAsync(X_out, dX, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, cb.st));
-    MVUS_HIP(hipStreamSynchronize(cb.st));
-    std::memcpy(P2_out, cand.P2[chosen], sizeof(double) * 12);
-  } catch (const HipError& e) {
-    g_create_error = e.msg;
-    return MVUS_E_HIP;
-  } catch (const std::exception& e) {
-    g_create_error = e.what();
-    return MVUS_E_INVALID;
-  }
-  return MVUS_OK;
-}
-
 }  // extern "C"

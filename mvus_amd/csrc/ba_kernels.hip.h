@@ -16,49 +16,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <dlfcn.h>
-
 #include <cstdlib>
 #include <string>
 
+#include "api_common.h"      // HipError, MVUS_HIP, RoctxRange
 #include "ba_math.h"
 #include "ba_solver.h"
 
 namespace mvus {
 
 constexpr int kThreads = 256;
-
-struct HipError { std::string msg; int code = -2; };   // code: the MVUS_E_* value the C ABI returns (-2 = MVUS_E_HIP)
-
-#define MVUS_HIP(expr)                                                                              \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) throw ::mvus::HipError{std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-// roctx ranges around the stages of a BA iteration (residual / linearise / solve / all-reduce) for rocprofv3 --marker-trace and the
-// ROCm timeline tools: libroctx64.so is opened at run time when MVUS_ROCTX=1 (no link-time dependency, no cost otherwise)
-struct RoctxApi {
-  int (*push)(const char*) = nullptr;
-  int (*pop)() = nullptr;
-  RoctxApi() {
-    if (!std::getenv("MVUS_ROCTX")) return;
-    void* lib = dlopen("libroctx64.so", RTLD_NOW | RTLD_LOCAL);
-    if (!lib) lib = dlopen("libroctx64.so.4", RTLD_NOW | RTLD_LOCAL);
-    if (!lib) return;
-    push = reinterpret_cast<int (*)(const char*)>(dlsym(lib, "roctxRangePushA"));
-    pop = reinterpret_cast<int (*)()>(dlsym(lib, "roctxRangePop"));
-    if (!push || !pop) { push = nullptr; pop = nullptr; }
-  }
-};
-inline RoctxApi& roctx_api() { static RoctxApi a; return a; }
-struct RoctxRange {
-  bool on;
-  explicit RoctxRange(const char* name) : on(roctx_api().push != nullptr) { if (on) roctx_api().push(name); }
-  ~RoctxRange() { if (on) roctx_api().pop(); }
-  RoctxRange(const RoctxRange&) = delete;
-  RoctxRange& operator=(const RoctxRange&) = delete;
-};
 
 struct DevProblem {  // trivially copyable: passed to kernels by value
   int C, P, NS, S, calib, undist, rs_free, sync_free, T, N;
