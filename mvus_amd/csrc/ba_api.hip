@@ -18,6 +18,7 @@
 #include "ba_kernels.hip.h"
 #include "ba_problem.h"
 #include "ba_solver.h"
+#include "ba_switches.h"
 #include "ba_schur_hip.hip.h"
 #include "ba_schur_host.hip.h"
 
@@ -74,6 +75,7 @@ struct HipBackend {
   int fd_ngroups = 0;
   double *fd_F = nullptr, *fd_h = nullptr, *fd_dx = nullptr, *fd_xg = nullptr;
   std::string err;
+  Switches sw;                       // ba_switches.h: read once, in init
 
   template <class T>
   T* dalloc(size_t count) {
@@ -90,6 +92,7 @@ struct HipBackend {
   }
 
   void init(const mvus_problem* p) {
+    sw = read_switches();
     device = p->device;
     MVUS_HIP(hipSetDevice(device));
     if (p->stream) stream = static_cast<hipStream_t>(p->stream);
@@ -300,7 +303,7 @@ struct HipBackend {
   int carry_jac_mode = -1;
   LmCarry lm_carry(int jac_mode) {
     LmCarry c{};
-    if (carry.f_valid && carry_seq + 1 == api_seq && !allreduce && !std::getenv("MVUS_LM_NO_CARRY")) {
+    if (carry.f_valid && carry_seq + 1 == api_seq && !allreduce && !sw.lm_no_carry) {
       c = carry;
       if (carry_jac_mode != jac_mode) c.lin_valid = false;
     }
@@ -318,7 +321,7 @@ struct HipBackend {
   double fetch_seq = 0.0;
   bool fetch_polled = false;
   bool fetch_poll_begin(double** mark, double* value) {
-    if (scal_map == nullptr || std::getenv("MVUS_FETCH_EVENT")) return false;      // (the mark itself is always written through mapped memory)
+    if (scal_map == nullptr || sw.fetch_event) return false;      // (the mark itself is always written through mapped memory)
     fetch_seq += 1.0;
     *mark = scal_map + kMarkSlot; *value = fetch_seq;
     fetch_polled = true;
@@ -334,7 +337,7 @@ struct HipBackend {
     MVUS_HIP(hipMemcpyAsync(scal_host + fq_off, src, sizeof(double) * k, hipMemcpyDeviceToHost, stream));
     fetch_queued = true;
   }
-  bool spec_on_shards() const { return scal_map != nullptr && std::getenv("MVUS_NO_SPEC_SHARDS") == nullptr; }
+  bool spec_on_shards() const { return scal_map != nullptr && !sw.no_spec_shards; }
   hipEvent_t fetch_ev = nullptr;
   bool fetch_marked = false;
   void fetch_mark() {
@@ -540,7 +543,7 @@ struct HipBackend {
     RoctxRange range("mvus residual");
     const int mb = hp.T > 0 ? (int)((hp.T + kThreads - 1) / kThreads) : 0;
     const size_t need = (size_t)dp.n_chunks + mb + 1;
-    const bool host_sum = scal_direct() && out >= scal_out() && out < scal_out() + 16 && !std::getenv("MVUS_SQ_DEVICE_SUM");
+    const bool host_sum = scal_direct() && out >= scal_out() && out < scal_out() + 16 && !sw.sq_device_sum;
     const int set = (out == lm_scalars()) ? 0 : 1;
     double* sq_part = this->sq_part;
     if (host_sum) {
@@ -764,8 +767,8 @@ struct HipBackend {
   double* lsmr_part = nullptr;             // [3][2048] partial sums (u.u, v.v, x.x) + beta
   double* lsmr_pu = nullptr;               // per-workgroup partials of |u'|^2 of the one-pass form (k_jvjtu)
   size_t lsmr_pu_cap = 0;
-  bool lsmr_on_device() const { return !allreduce && std::getenv("MVUS_LSMR_HOST") == nullptr; }
-  bool lsmr_scaled_on_device() const { return std::getenv("MVUS_LSMR_BOUNDED_HOST") == nullptr; }      // (A/B: the bounded problem on the host-driven loop, rounds 3-5)
+  bool lsmr_on_device() const { return !allreduce && !sw.lsmr_host; }
+  bool lsmr_scaled_on_device() const { return !sw.lsmr_bounded_host; }      // (A/B: the bounded problem on the host-driven loop, rounds 3-5)
   // D, E: the column scaling and the extra diagonal rows of the bounded problem (trf_bounds), device n-vectors or null; ub: the n extra rows of u
   void lsmr_iterations(LsmrScalars& sc, double* ut, double* tm, double* v, double* tn, double* h, double* hbar, double* x,
                        const double* D = nullptr, const double* E = nullptr, double* ub = nullptr) {
@@ -789,7 +792,7 @@ struct HipBackend {
     // MVUS_LSMR_ONE_PASS=1: one pass over J per iteration (k_jvjtu: u kept unnormalised, its norm in *ubeta).  Opt-in: the converged
     // answers stay inside the parity bars either way, but the unconverged 10-evaluation iterate of one fixture (dist_fixed_2cam) moves
     // outside the bars measured with the two-pass arithmetic
-    const bool one_pass = dp.n_chunks > 0 && !scaled && std::getenv("MVUS_LSMR_ONE_PASS") != nullptr;
+    const bool one_pass = dp.n_chunks > 0 && !scaled && lsmr_one_pass_now();
     const unsigned gj = (unsigned)(xcd_grid(dp.n_chunks) + (hp.T > 0 ? (hp.T + kThreads - 1) / kThreads : 0));
     double* ubeta = beta_dev + 1;
     if (one_pass) {

@@ -35,6 +35,8 @@
 #include <limits>
 #include <vector>
 
+#include "ba_switches.h"
+
 namespace mvus {
 
 struct SolveOptions {
@@ -398,7 +400,7 @@ struct Lsmr {
   int run(const double* D, const double* E, const double* b_top, double damp, double atol, double btol, double conlim,
           int64_t maxiter, double* x, int* itn_out) {
     using detail::sym_ortho;
-    const bool trace = std::getenv("MVUS_LSMR_TRACE") != nullptr;
+    const bool trace = lsmr_trace_now();
     be.copy(ut, b_top, m);
     if (E) be.fill(ub, 0.0, n);
     const double normb = std::sqrt(be.dot_m(ut, ut));

@@ -2,6 +2,7 @@
 // Lets the CPU test-suite check the arithmetic the HIP kernels run (residual, analytic Jacobian)
 // against the oracle without a GPU.  Never linked into libmvusba.so.
 #include "../../mvus_amd/csrc/ba_math.h"
+#include "../../mvus_amd/csrc/ba_switches.h"
 #include "../../mvus_amd/csrc/triangulate.hip.h"
 #include "../../mvus_amd/csrc/spline_fit.hip.h"
 #include "../../mvus_amd/csrc/pnp.hip.h"
@@ -110,4 +111,21 @@ extern "C" int hostcheck_fm_seven_point(const double* xs /* [7][4] */, double* F
 // x1, x2: [2][N]; err[N]
 extern "C" void hostcheck_fm_error(long long N, const double* F, const double* x1, const double* x2, double* err) {
   for (long long i = 0; i < N; ++i) err[i] = fm_error(F, x1[i], x1[N + i], x2[i], x2[N + i]);
+}
+
+// ---- the switch table of the BA unit (ba_switches.h): the field behind an MVUS_* variable, read from the environment now ----
+// bools as 0 / 1; -2 for a name the table does not have
+extern "C" long long hostcheck_switch(const char* name) {
+  const Switches s = read_switches();
+  const struct { const char* name; long long value; } fields[] = {
+      {"MVUS_LM_NO_CARRY", s.lm_no_carry}, {"MVUS_FETCH_EVENT", s.fetch_event}, {"MVUS_NO_SPEC_SHARDS", s.no_spec_shards},
+      {"MVUS_SQ_DEVICE_SUM", s.sq_device_sum}, {"MVUS_LSMR_HOST", s.lsmr_host}, {"MVUS_LSMR_BOUNDED_HOST", s.lsmr_bounded_host},
+      {"MVUS_LSMR_ONE_PASS", s.lsmr_one_pass}, {"MVUS_LSMR_TRACE", s.lsmr_trace}, {"MVUS_GEMM_SLABS", s.gemm_slabs}, {"MVUS_RCS", s.rcs_gj},
+      {"MVUS_RCS_TRSM", s.rcs_trsm_launch}, {"MVUS_RCS_SPIN_LIMIT", s.rcs_spin_limit}, {"MVUS_BCR_FUSED", s.bcr_fused},
+      {"MVUS_PART_LEN", s.part_len}, {"MVUS_PART_BACK", s.part_back}, {"MVUS_DIRECT_RHS", s.direct_rhs},
+      {"MVUS_SEP_SEQUENTIAL", s.sep_sequential}, {"MVUS_SEP_TWO_LEVEL", s.sep_two_level}, {"MVUS_ASM_ATOMIC", s.asm_atomic},
+      {"MVUS_WIN", s.win}, {"MVUS_WIN_GROUPS", s.win_groups}, {"MVUS_NO_SPEC", s.no_spec}, {"MVUS_LM_MATERIALIZE_J", s.lm_materialize_j},
+      {"MVUS_NE_FROM_J", s.ne_from_j}, {"MVUS_NO_OVERLAP", s.no_overlap}, {"MVUS_DEBUG", s.debug}};
+  for (const auto& f : fields) if (std::strcmp(f.name, name) == 0) return f.value;
+  return -2;
 }

@@ -10,7 +10,7 @@ from mvus_amd import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = [os.path.join(HERE, 'hostcheck', f) for f in ('hostcheck.cpp', 'host_backend.cpp')]
-DEPS = SRC + [os.path.join(ROOT, 'mvus_amd', 'csrc', f) for f in ('ba_math.h', 'ba_solver.h', 'ba_problem.h', 'ba_schur.h', 'ba_partition.h', 'triangulate.hip.h', 'spline_fit.hip.h', 'pnp.hip.h', 'epipolar.hip.h')] \
+DEPS = SRC + [os.path.join(ROOT, 'mvus_amd', 'csrc', f) for f in ('ba_math.h', 'ba_switches.h', 'ba_solver.h', 'ba_problem.h', 'ba_schur.h', 'ba_partition.h', 'triangulate.hip.h', 'spline_fit.hip.h', 'pnp.hip.h', 'epipolar.hip.h')] \
     + [os.path.join(ROOT, 'include', 'mvus_ba.h')]
 SO = os.path.join(HERE, 'hostcheck', 'libhostcheck.so')
 
@@ -58,6 +58,8 @@ def load():
     lib.hostcheck_fm_cubic_roots.argtypes = [_lib.c_double_p, _lib.c_double_p]
     lib.hostcheck_fm_seven_point.argtypes = [_lib.c_double_p, _lib.c_double_p]
     lib.hostcheck_fm_error.argtypes = [ctypes.c_longlong] + [_lib.c_double_p] * 4
+    lib.hostcheck_switch.restype = ctypes.c_longlong
+    lib.hostcheck_switch.argtypes = [ctypes.c_char_p]
     _cached = lib
     return lib
 
