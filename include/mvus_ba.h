@@ -147,7 +147,7 @@ void mvus_default_opts(mvus_solve_opts* opts);
  * sizeof(mvus_result), sizeof(mvus_problem) as this library was compiled (any pointer may be NULL) and returns MVUS_ABI_VERSION.  A
  * binding asserts these against its own struct definitions at load time -- mvus_solve_opts has grown over the rounds (lm_lambda_min,
  * lm_trust_radius) and a stale stub would otherwise hand the library a short buffer.  The version is raised whenever a struct or an
- * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen) does not raise
+ * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance) does not raise
  * it -- a binding that needs one finds it missing at load time.  Stateless, no device is touched.  No reference counterpart (the reference has no FFI). */
 #define MVUS_ABI_VERSION 8
 int32_t mvus_abi_sizes(int32_t* solve_opts_size, int32_t* result_size, int32_t* problem_size);
@@ -284,6 +284,33 @@ int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* w
 int mvus_ba_set_frozen(mvus_ba* h, const uint8_t* frozen, int64_t count);
 int64_t mvus_ba_num_frozen(const mvus_ba* h);
 
+/* Covariance of the estimate at x (ba_cov.hip.h; no reference counterpart: scipy's least_squares returns none either).  With the loss and the
+ * frozen mask in force, H is the matrix mvus_ba_normal_equations exports at x -- J^T J, or scipy's J^T diag(s^2) J under a robust loss (the
+ * usual Gauss-Newton approximation then), the motion rows included as the prior they are.  An unknown is ESTIMATED when it is not frozen and
+ * its diagonal entry of H is non-zero (not: rs without rolling shutter, a control-point coordinate no row touches);
+ *   Sigma = sigma^2 (H restricted to the estimated unknowns)^-1, rows and columns of the others exactly 0.
+ * sigma2 > 0: the caller's variance factor; otherwise the a-posteriori one, 2 cost / (m_act - n_est) -- cost the (robust) cost at x, m_act the
+ * rows of f with a non-empty Jacobian row (every motion row, both rows of every detection with a span), n_est the estimated unknowns
+ * (MVUS_E_INVALID when m_act <= n_est).  Outputs (any may be NULL):
+ *   cov_cam[CB * CB], CB = C * (3 + P): the camera-side block, in the order of the head of x -- alpha(C), beta(C), rs(C), then P per camera
+ *     (the order of mvus_ba_set_frozen);
+ *   cov_band[N][4][3][3]: blocks (p, p + w), w = 0..3, of the control points' block in control-point order (p = index over all splines,
+ *     coordinates x, y, z inside a block), zero where p + w >= N -- what the covariance of any point of the trajectory needs
+ *     (mvus_spline_cov_eval); camera-trajectory cross-covariances are not returned;
+ *   estimated[n] in the order of x;  *sigma2_out the factor used;  *dof_out = m_act - n_est.
+ * H is singular while the similarity gauge is free: a pivot p_k <= 1e-10 H_kk of either factorisation (spline block, reduced camera system)
+ * returns MVUS_E_NUMERIC with a message that names the unknown -- fix the gauge with mvus_ba_set_frozen (settings ba_gauge: "anchor" /
+ * ba_freeze).  Below that bound fewer than about six digits of a variance survive fp64.  MVUS_E_UNSUPPORTED: a sharded handle ("sharded" in
+ * the message), more than 1152 camera-side unknowns, a band wider than 16 control points.  Computed on the device only (no CPU fallback).
+ * The call drops what an LM solve carried over (cost, blocks, the speculative linearisation) exactly as mvus_ba_set_loss does and leaves the
+ * damping history alone: a later solve returns the bits it would have returned without the call.  Like mvus_ba_residual_jacobian it leaves
+ * the analytic Jacobian of x held. */
+int mvus_ba_covariance(mvus_ba* h, const double* x, double sigma2, double* cov_cam, double* cov_band, uint8_t* estimated,
+                       double* sigma2_out, int64_t* dof_out);
+/* Measurement hook: milliseconds (HIP events) of the stages of the LAST mvus_ba_covariance on the handle and their names, the first `count`
+ * of them; returns the number of stages, or MVUS_E_INVALID before the first call. */
+int32_t mvus_ba_covariance_stage_ms(mvus_ba* h, double* ms_out, const char** names_out, int32_t count);
+
 /* The least_squares call of Scene.BA (common.py:670) -- x is read and overwritten with res.x.
  * lb/ub come from opts of the problem (rs_bounds).  f_out[m] may be NULL.  x, res and f_out are complete on return.  MVUS_SOLVER_LM_SCHUR
  * with f_out == NULL may return while device work for the NEXT call is still running on the handle's stream (the linearisation at the
@@ -367,6 +394,13 @@ int mvus_triangulate(int32_t device, int64_t N, const double* x1, const double* 
  * Same recurrence as scipy.interpolate.splev (FITPACK splev.f / fpbspl.f).  Stateless; no CPU fallback. */
 int mvus_spline_eval(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
                      const double* coefs, int64_t nt, const double* t, double* X, int32_t* which);
+
+/* Covariance of trajectory samples from mvus_ba_covariance's cov_band[N][4][3][3] (N = all control points, the splines one behind the other as
+ * in x): for each of the nt timestamps  Cov X(t) = sum_{a,b} h_a(t) h_b(t) Sigma(p + a, p + b)  over the four control points p .. p + 3 of its
+ * knot span, h the basis values mvus_spline_eval uses.  cov[nt * 9]: a row-major 3 x 3 per sample, NaN where which = -1 (outside every
+ * interval, closed like mvus_spline_eval).  Arguments as mvus_spline_eval.  One lane per sample; stateless; no CPU fallback. */
+int mvus_spline_cov_eval(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
+                         const double* cov_band, int64_t nt, const double* t, double* cov, int32_t* which);
 
 /* Least-squares cubic spline on a FIXED knot vector (num_knots = n + 4, first/last four equal): coefs[3*n] (cx cy cz)
  * minimising sum_i |X(t_i) - X_i|^2 over the m data points t[m], X[3*m] (x(m) y(m) z(m)), t inside [knots[3], knots[n]].

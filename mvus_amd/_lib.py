@@ -87,6 +87,8 @@ API = [
     ('mvus_ba_set_frozen', ctypes.c_int, [ctypes.c_void_p, c_uint8_p, ctypes.c_int64]),
     ('mvus_ba_num_frozen', ctypes.c_int64, [ctypes.c_void_p]),
     ('mvus_ba_robust_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ('mvus_ba_covariance', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_double_p, c_double_p, c_uint8_p, c_double_p, c_int64_p]),
+    ('mvus_ba_covariance_stage_ms', ctypes.c_int32, [ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32]),
     ('mvus_ba_solve', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.POINTER(MvusSolveOpts), ctypes.POINTER(MvusResult), c_double_p]),
     ('mvus_ba_outlier_mask', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_uint8_p]),
     ('mvus_ba_remove_outliers', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_uint8_p, c_int64_p]),
@@ -99,6 +101,7 @@ API = [
     ('mvus_ba_time_kernel', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_double_p]),
     ('mvus_ba_set_x', ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     ('mvus_spline_eval', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p, c_double_p, c_int32_p]),
+    ('mvus_spline_cov_eval', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p, c_double_p, c_int32_p]),
     ('mvus_spline_lsq', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
     ('mvus_spline_smooth', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_double, c_int32_p, c_double_p, c_double_p,
                                           c_double_p, c_int32_p]),

@@ -270,6 +270,30 @@ class BAHandle:
                     'mvus_ba_robust_cost')
         return (cost.value, w) if weights else cost.value
 
+    def covariance(self, x, sigma2=None):
+        """Covariance of the estimate at x (mvus_ba_covariance) under the loss and the frozen mask in force: a namespace with
+        ``cam`` [CB, CB] in the order of the head of x (alpha(C), beta(C), rs(C), P per camera), ``band`` [N, 4, 3, 3] (blocks (p, p + w) of
+        the control points, control-point order), ``estimated`` bool[n] in the order of x, ``sigma2`` (the caller's when given and > 0, else
+        2 cost / dof) and ``dof``.  Rows and columns of unknowns that are not estimated are exactly 0.  A free gauge raises ValueError
+        (MVUS_E_NUMERIC) with "gauge" in the message."""
+        x = self._x(x, self.n)
+        CB, N = self.prob.C * (3 + self.prob.P), int(self.prob.n_coef.sum())
+        cam = np.empty((CB, CB))
+        band = np.empty((N, 4, 3, 3))
+        est = np.empty(self.n, dtype=np.uint8)
+        s2, dof = ctypes.c_double(0.0), ctypes.c_int64(0)
+        self._check(self.lib.mvus_ba_covariance(self.h, _lib.dptr(x), 0.0 if sigma2 is None else float(sigma2), _lib.dptr(cam), _lib.dptr(band),
+                                                est.ctypes.data_as(_lib.c_uint8_p), ctypes.byref(s2), ctypes.byref(dof)), 'mvus_ba_covariance')
+        return SimpleNamespace(cam=cam, band=band, estimated=est.astype(bool), sigma2=s2.value, dof=int(dof.value))
+
+    def covariance_stage_ms(self):
+        """[(stage name, milliseconds)] of the last ``covariance`` call on the handle (HIP events)."""
+        ms = (ctypes.c_double * 16)()
+        names = (ctypes.c_char_p * 16)()
+        k = self.lib.mvus_ba_covariance_stage_ms(self.h, ms, names, 16)
+        self._check(min(k, 0), 'mvus_ba_covariance_stage_ms')
+        return [(names[i].decode(), ms[i]) for i in range(k)]
+
     def solve(self, x0, solver=SOLVER_TRF_LSMR, jac_mode=JAC_PATTERN, max_nfev=10, opts=None, return_fun=True,
               ties='numpy', matrix=None, prepared=False):
         """The least_squares call of Scene.BA.  Returns an OptimizeResult-like namespace

@@ -21,6 +21,7 @@
 #include "ba_switches.h"
 #include "ba_schur_hip.hip.h"
 #include "ba_schur_host.hip.h"
+#include "ba_cov.hip.h"
 
 namespace mvus {
 
@@ -860,6 +861,7 @@ struct mvus_rccl_handle { void* comm = nullptr; };
 struct mvus_ba {
   HipBackend be;
   std::unique_ptr<HipSchur<HipBackend>> schur;   // normal-equation workspace, built on first use
+  std::unique_ptr<CovChain<HipBackend>> cov;     // buffers of mvus_ba_covariance (ba_cov.hip.h), built on first use
   mvus_rccl_handle rccl;                         // communicator of mvus_ba_set_rccl (destroyed with the handle)
   ~mvus_ba();
 };
@@ -1275,6 +1277,44 @@ int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* w
   });
 }
 
+int mvus_ba_covariance(mvus_ba* h, const double* x, double sigma2, double* cov_cam, double* cov_band, uint8_t* estimated,
+                       double* sigma2_out, int64_t* dof_out) {
+  return guarded(h, [&] {
+    HipBackend& be = h->be;
+    if (!x || !std::isfinite(sigma2)) { be.err = "covariance: x is NULL or sigma2 is not finite"; return MVUS_E_INVALID; }
+    if (be.allreduce || be.tshard.on) { be.err = "covariance: not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
+    // what an LM solve left for its point (cost, blocks, the speculative linearisation) is dropped as mvus_ba_set_loss drops it -- the blocks
+    // are overwritten below; the damping history stays: a later solve returns the bits it would have returned without this call
+    be.carry = LmCarry{};
+    if (be.hp.C * (3 + be.hp.P) > 1152) { be.err = "covariance: more than 1152 camera-side unknowns"; return MVUS_E_UNSUPPORTED; }
+    if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
+    if (!h->cov) h->cov.reset(new CovChain<HipBackend>(be));
+    // the (robust) cost at x, then the analytic Jacobian of x held as mvus_ba_residual_jacobian holds it
+    be.upload(be.x_cur, x, be.hp.n);
+    be.residual_sq(be.x_cur, be.f_cur, be.scal_out() + 3);
+    double twice = 0;
+    be.fetch(be.scal_out() + 3, 1, &twice);
+    if (!std::isfinite(twice)) { be.err = "covariance: residuals are not finite at x"; return MVUS_E_NUMERIC; }
+    be.jacobian(be.x_cur, be.f_cur, MVUS_JAC_ANALYTIC);
+    be.held_analytic_at_xcur = true;
+    CovResult res;
+    const int rc = h->cov->run(*h->schur, 0.5 * twice, sigma2, cov_cam, cov_band, estimated, res);
+    if (rc != MVUS_OK) return rc;
+    if (sigma2_out) *sigma2_out = res.sigma2;
+    if (dof_out) *dof_out = res.dof;
+    return MVUS_OK;
+  });
+}
+
+int32_t mvus_ba_covariance_stage_ms(mvus_ba* h, double* ms_out, const char** names_out, int32_t count) {
+  if (!h || !h->cov || !h->cov->timed) return MVUS_E_INVALID;
+  for (int s = 0; s < count && s < kCovStages; ++s) {
+    if (ms_out) ms_out[s] = h->cov->stage_ms[s];
+    if (names_out) names_out[s] = cov_stage_name(s);
+  }
+  return kCovStages;
+}
+
 int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
   return guarded(h, [&] {
     HipBackend& be = h->be;
@@ -1472,6 +1512,7 @@ int mvus_ba_set_allreduce(mvus_ba* h, mvus_allreduce_fn fn, void* user, int32_t 
 
 }  // extern "C"
 mvus_ba::~mvus_ba() {
+  cov.reset();
   schur.reset();
   if (rccl.comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(be.stream); (void)g_rccl.CommDestroy(rccl.comm); }
 }

@@ -100,6 +100,36 @@ int mvus_spline_eval(int32_t device, int32_t S, const double* interval, const in
   });
 }
 
+int mvus_spline_cov_eval(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
+                         const double* cov_band, int64_t nt, const double* t, double* cov, int32_t* which) {
+  if (S < 1 || !interval || !knot_offsets || !knots || !cov_band || nt < 0 || (nt > 0 && (!t || !cov || !which))) { g_create_error = "spline_cov_eval: bad arguments"; return MVUS_E_INVALID; }
+  for (int s = 0; s < S; ++s)
+    if (knot_offsets[s + 1] - knot_offsets[s] < 8) { g_create_error = "spline_cov_eval: a cubic spline needs at least 8 knots"; return MVUS_E_INVALID; }
+  if (nt == 0) return MVUS_OK;
+  return stateless([&] {
+    CallBuffers cb;
+    cb.open(device);
+    std::vector<long long> koff(knot_offsets, knot_offsets + S + 1), coff(S + 1, 0);
+    for (int s = 0; s < S; ++s) coff[s + 1] = coff[s] + (koff[s + 1] - koff[s] - 4);        // control points, not coefficients
+    SplineSet sp;
+    sp.S = S;
+    sp.istart = cb.put(interval, (size_t)S); sp.iend = cb.put(interval + S, (size_t)S);
+    sp.knot_off = cb.put(koff.data(), koff.size()); sp.knots = cb.put(knots, (size_t)koff[S]);
+    sp.coef_off = nullptr; sp.coefs = nullptr;
+    const long long* dcoff = cb.put(coff.data(), coff.size());
+    const double* dband = cb.put(cov_band, (size_t)coff[S] * 36);
+    const double* dt = cb.put(t, (size_t)nt);
+    double* dC = cb.get<double>(9 * (size_t)nt);
+    int32_t* dw = cb.get<int32_t>((size_t)nt);
+    hipLaunchKernelGGL(k_spline_cov_eval, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, cb.st, sp, dcoff, dband, (long long)nt, dt, dC, dw);
+    MVUS_HIP(hipGetLastError());
+    MVUS_HIP(hipMemcpyAsync(cov, dC, sizeof(double) * 9 * nt, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipMemcpyAsync(which, dw, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipStreamSynchronize(cb.st));
+    return MVUS_OK;
+  });
+}
+
 int mvus_spline_lsq(int32_t device, int32_t num_knots, const double* knots, int64_t m, const double* t, const double* X, double* coefs) {
   const int n = num_knots - 4;
   if (num_knots < 8 || !knots || m < 1 || !t || !X || !coefs) { g_create_error = "spline_lsq: bad arguments"; return MVUS_E_INVALID; }

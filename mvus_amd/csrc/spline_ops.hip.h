@@ -7,8 +7,10 @@
 //                     Cholesky solve by one wavefront.  The reference's traj_to_spline lets FITPACK choose the knots
 //                     adaptively inside its smooth_factor loop (common.py:224-270); that search stays on the host
 //                     (Scene.traj_to_spline), this is the refit on the knots it found -- scipy's make_lsq_spline is the oracle.
+//   k_spline_cov_eval the covariance of the same samples from the control points' band of mvus_ba_covariance (cov_spline_sample)
 #pragma once
 #include "ba_math.h"
+#include "ba_cov_math.h"
 
 namespace mvus {
 
@@ -44,6 +46,33 @@ __global__ __launch_bounds__(256) void k_spline_eval(SplineSet sp, long long nt,
     for (int q = 0; q < 4; ++q) { o0 = o0 + c[q] * h[q]; o1 = o1 + c[n + q] * h[q]; o2 = o2 + c[2 * n + q] * h[q]; }
   }
   X[i] = o0; X[nt + i] = o1; X[2 * nt + i] = o2;
+}
+
+// Cov X(t) per sample from band[N][4][3][3] (blocks (p, p + w) of the control points' covariance, p over all splines): one lane per
+// sample, NaN outside every interval.  ctrl_off[s] = index of spline s' first control point.
+__global__ __launch_bounds__(256) void k_spline_cov_eval(SplineSet sp, const long long* __restrict__ ctrl_off, const double* __restrict__ band, long long nt,
+                                                         const double* __restrict__ t, double* __restrict__ cov, int32_t* __restrict__ which) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= nt) return;
+  const double x = t[i];
+  int lo = 0, hi = sp.S;
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (x >= sp.istart[mid]) lo = mid; else hi = mid; }
+  const bool in = x >= sp.istart[lo] && x <= sp.iend[lo];
+  which[i] = in ? lo : -1;
+  double o[9];
+  if (in) {
+    const double* k = sp.knots + sp.knot_off[lo];
+    const int n = (int)(sp.knot_off[lo + 1] - sp.knot_off[lo]) - 4;
+    const int l = find_span(k, n, x);
+    double h[4], dh[4];
+    bspline_basis<false>(k, l, x, h, dh);
+    cov_spline_sample(h, band + (ctrl_off[lo] + (l - 3)) * 36, o);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) o[e] = __builtin_nan("");
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) cov[i * 9 + e] = o[e];
 }
 
 // ---- least squares on fixed knots ------------------------------------------------------------------------------------

@@ -188,7 +188,7 @@ def evaluate_against_truth(flight, sc):
 def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output=True):
     """main.py:18-93 from the config.json at ``path`` (the reference's schema; ``create_scene``): every stage through
     ``StageTimer`` -- create_scene, cut_detection, init_alpha, time_shift, detection_to_global, init_traj(error=thres_Fmatix),
-    traj_to_spline, the incremental loop, spline_to_traj; ``align_gt`` when the config gives ground truth; the Scene pickled to
+    traj_to_spline, the incremental loop, spline_to_traj; ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true; ``align_gt`` when the config gives ground truth; the Scene pickled to
     ``settings['path_output']`` when ``output`` and that key is set.  Returns (Scene, StageTimer)."""
     from .reconstruction import common
     timer = timer or StageTimer()
@@ -202,6 +202,10 @@ def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output
     timer.run('traj_to_spline', 2, flight.traj_to_spline, smooth_factor=st['smooth_factor'])
     incremental_reconstruction(flight, max_iter=max_iter, verbose=verbose, timer=timer)
     flight.out = {'reconst_tran': flight.traj[1:]}
+    if flight.ba_covariance_enabled():
+        # settings['ba_covariance']: the covariance of the last BA's problem (all cameras of the sequence), carried by the pickle as flight.covariance
+        timer.run('ba_covariance', flight.numCam, flight.ba_covariance, list(flight.sequence[:flight.numCam if flight.find_order else len(flight.sequence)]), rs=st['rolling_shutter'], motion_reg=st['motion_reg'],
+                  motion_weights=st['motion_weights'], rs_bounds=st['rs_bounds'])
     if flight.gt:
         from .analysis.compare_gt import align_gt
         flight.out = timer.run('align_gt', flight.numCam, align_gt, flight, flight.gt['frequency'], flight.gt['filepath'], visualize=False)

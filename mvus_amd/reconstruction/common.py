@@ -40,6 +40,8 @@ Extra ``settings`` keys (all optional; a reference ``config.json`` has none of t
 ``ba_gauge``   'free' (DEFAULT: the reference's problem, similarity gauge left to the solver) or 'anchor': the pose of ``sequence[0]`` and
                one translation component of ``sequence[1]`` are held -- the seven degrees of freedom of the similarity, no more
                (``Scene.ba_frozen_mask``).
+``ba_covariance`` True: ``mvus_amd.pipeline.reconstruct_from_config`` calls ``Scene.ba_covariance`` after the last BA and the output pickle carries
+               its dict (``Scene.covariance``).  DEFAULT False: nothing changes.  Needs a fixed gauge (``ba_gauge: 'anchor'`` or ``ba_freeze``).
 ``ba_deterministic`` accepted and ignored: the 'lm' solver's normal equations are assembled without floating-point atomics
                (one writer, one order of additions per entry) -- the same bits on every run by construction.
 ``opt_sync`` (reference key: False freezes alpha/beta), ``device``.
@@ -510,7 +512,65 @@ class Scene:
             raise ValueError("settings['ba_jacobian'] must be one of %s, not %r" % (sorted(modes), jac))
         self.ba_loss()                       # (validated with the rest: a bad ba_loss / ba_f_scale raises before any GPU call)
         self.ba_freeze()                     # (and ba_freeze / ba_gauge)
+        self.ba_covariance_enabled()         # (and ba_covariance)
         return solver, modes[jac]
+
+    def ba_covariance_enabled(self):
+        """settings['ba_covariance'] validated (a bool; absent = False): host only."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        v = st.get('ba_covariance', False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("settings['ba_covariance'] must be true or false, not %r" % (v,))
+        return bool(v)
+
+    def ba_param_names(self):
+        """Names of the P parameters of one camera in x (Camera.P2vector order)."""
+        if self.settings['opt_calib']:
+            return ['fx', 'fy', 'cx', 'cy', 'r1', 'r2', 'r3', 't1', 't2', 't3', 'k1', 'k2', 'p1', 'p2', 'k3']
+        return ['r1', 'r2', 'r3', 't1', 't2', 't3']
+
+    def ba_covariance(self, cams, t=None, sigma2=None, rs=False, motion_reg=False, motion_weights=1, rs_bounds=False):
+        """Covariance of the BA estimate over the cameras ``cams`` at the scene's current state (``mvus_ba_covariance``): built on the
+        handle the last BA left resident when it still describes that problem (else a new one), with the loss and the frozen mask of the
+        settings.  The gauge must be fixed (``ba_gauge: 'anchor'`` / ``ba_freeze``), else ValueError.  ``t``: timestamps of the position
+        covariance (default: the stamps of ``spline_to_traj``, ``self.traj[0]``); ``sigma2``: the variance factor (default: a posteriori).
+        Stores and returns a data-only dict:
+          cams, param_names, sigma2, dof,
+          cam_cov [CB, CB] in the order of the head of x (alpha(C), beta(C), rs(C), P per camera), estimated_cam bool[CB],
+          cam_std {camera: {'alpha', 'beta', 'rs', <parameter names>}: standard deviation},
+          band [N, 4, 3, 3] blocks (p, p + w) of the control points' covariance,
+          t, pos_cov [len(t), 3, 3], pos_std [len(t), 3] (1-sigma per axis; NaN outside every interval)."""
+        from .. import spline as _spline
+        cams = list(cams)
+        self.alpha, self.beta, self.rs = (np.asarray(v, dtype=np.float64) for v in (self.alpha, self.beta, self.rs))
+        prob = self._ba_problem(cams, rs=rs, motion_reg=motion_reg, motion_weights=motion_weights, rs_bounds=rs_bounds)
+        x = self._pack(prob, cams)
+        self.ba_mode()                             # validates the ba_* settings
+        loss, f_scale = self.ba_loss()
+        h = self._resident_handle(prob, cams)
+        if h.loss != (loss, f_scale):
+            h.set_loss(loss, f_scale)
+        mask, cur = self.ba_frozen_mask(cams), h.frozen
+        if not np.array_equal(mask, cur if cur is not None else np.zeros(mask.size, dtype=bool)):
+            h.set_frozen(mask)
+        cv = h.covariance(x, sigma2=sigma2)
+        C, P = len(cams), prob.P
+        names = self.ba_param_names()
+        sd = np.sqrt(np.diag(cv.cam))
+        cam_std = {}
+        for k, cam in enumerate(cams):
+            d = {'alpha': float(sd[k]), 'beta': float(sd[C + k]), 'rs': float(sd[2 * C + k])}
+            d.update({name: float(sd[3 * C + k * P + j]) for j, name in enumerate(names)})
+            cam_std[int(cam)] = d
+        ts = np.asarray(self.traj[0] if t is None else t, dtype=np.float64)
+        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
+        pos_cov, _ = _spline.cov_evaluate(self.spline['tck'], self.spline['int'], cv.band, ts, device=device)
+        with np.errstate(invalid='ignore'):
+            pos_std = np.sqrt(np.einsum('tii->ti', pos_cov))
+        self.covariance = {'cams': [int(c) for c in cams], 'param_names': names, 'sigma2': float(cv.sigma2), 'dof': int(cv.dof),
+                           'cam_cov': cv.cam, 'estimated_cam': cv.estimated[:C * (3 + P)].copy(), 'cam_std': cam_std, 'band': cv.band,
+                           't': ts.copy(), 'pos_cov': pos_cov, 'pos_std': pos_std}
+        return self.covariance
 
     FREEZE_NAMES = ('alpha', 'beta', 'rs', 'R', 't', 'K', 'd')
 

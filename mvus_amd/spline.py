@@ -40,6 +40,31 @@ def evaluate(tck, interval, t, device=0):
     return X, which
 
 
+def cov_evaluate(tck, interval, band, t, device=0):
+    """Covariance of the spline points at timestamps ``t`` from ``band`` [N, 4, 3, 3] -- the control points' band of
+    ``BAHandle.covariance`` (N = all control points, the splines one behind the other): ``mvus_spline_cov_eval``.  Returns
+    (cov[len(t), 3, 3], which[len(t)]); NaN where which = -1 (outside every interval)."""
+    lib = _lib.load()
+    interval = np.ascontiguousarray(np.asarray(interval, dtype=np.float64))
+    S = interval.shape[1]
+    knots = [np.asarray(k[0], dtype=np.float64) for k in tck]
+    koff = np.concatenate(([0], np.cumsum([k.size for k in knots]))).astype(np.int64)
+    kn = np.ascontiguousarray(np.concatenate(knots))
+    band = np.ascontiguousarray(band, dtype=np.float64)
+    if band.shape != (int(koff[-1]) - 4 * S, 4, 3, 3):
+        raise ValueError('band has shape %s, expected (%d, 4, 3, 3)' % (band.shape, int(koff[-1]) - 4 * S))
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    if t.ndim != 1:
+        raise ValueError('Input timestamps must be a 1D array')
+    cov = np.full((t.size, 3, 3), np.nan)
+    which = np.full(t.size, -1, dtype=np.int32)
+    rc = lib.mvus_spline_cov_eval(int(device), int(S), _lib.dptr(interval), koff.ctypes.data_as(_lib.c_int64_p), _lib.dptr(kn), _lib.dptr(band),
+                                  t.size, _lib.dptr(t), _lib.dptr(cov), which.ctypes.data_as(_lib.c_int32_p))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_cov_eval')
+    return cov, which
+
+
 def lsq_fit(knots, t, X, device=0):
     """Coefficients [cx, cy, cz] of the least-squares cubic spline with knot vector ``knots`` through the points X[3, m] at t[m]."""
     lib = _lib.load()
