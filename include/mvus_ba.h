@@ -402,6 +402,28 @@ int mvus_spline_eval(int32_t device, int32_t S, const double* interval, const in
 int mvus_spline_cov_eval(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
                          const double* cov_band, int64_t nt, const double* t, double* cov, int32_t* which);
 
+/* Kinematics of the trajectory (arguments, checks and `which` as mvus_spline_eval; one lane per sample; stateless; no CPU fallback).
+ *
+ * mvus_spline_eval_der: X and its first nder derivatives in the spline parameter (nder = 0, 1 or 2, else MVUS_E_INVALID).
+ * D[(nder + 1) * 3 * nt], order-major and inside an order x(nt) y(nt) z(nt) as X of mvus_spline_eval, whose bits the order-0 block has;
+ * 0 where which = -1.  All orders come from one span search and one run of the FITPACK recurrence (splder.f / fpader.f for the second).
+ * On a knot the derivatives are those from the right, at the last knot of a spline those from the left, as scipy's splev(der=). */
+int mvus_spline_eval_der(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
+                         const double* coefs, int64_t nt, const double* t, int32_t nder, double* D, int32_t* which);
+
+/* Covariance of the state (X, X', .., D^nder X) of each sample from cov_band[N][4][3][3] (as mvus_spline_cov_eval): with Dn = 3 (nder + 1),
+ * component 3 i + r = coordinate r of derivative i,  Cov(D^i X, D^j X) = sum_{a,b} h^(i)_a h^(j)_b Sigma(p + a, p + b).  cov[nt * Dn * Dn],
+ * a row-major Dn x Dn per sample, symmetric to the bit, NaN where which = -1.  nder as above. */
+int mvus_spline_kin_cov_eval(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
+                             const double* cov_band, int64_t nt, const double* t, int32_t nder, double* cov, int32_t* which);
+
+/* Distance flown: dist[nt] = the length of the curve from the start of the sample's interval to the sample (exactly 0 at the start, and
+ * where which = -1); total[S] (may be NULL) = the length of each interval.  Every knot span is integrated by an 8-point Gauss-Legendre rule
+ * (|X'| is not a polynomial: the rule degrades where the speed passes through zero inside a span), the spans are summed in their order
+ * without atomics: the same bits on every run, and total[s] is dist at the interval's end to the bit. */
+int mvus_spline_length(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
+                       const double* coefs, int64_t nt, const double* t, double* dist, int32_t* which, double* total);
+
 /* Least-squares cubic spline on a FIXED knot vector (num_knots = n + 4, first/last four equal): coefs[3*n] (cx cy cz)
  * minimising sum_i |X(t_i) - X_i|^2 over the m data points t[m], X[3*m] (x(m) y(m) z(m)), t inside [knots[3], knots[n]].
  * The coefficient refit of Scene.traj_to_spline (common.py:224-270) once FITPACK's adaptive search has placed the knots (that

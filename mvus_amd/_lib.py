@@ -102,6 +102,12 @@ API = [
     ('mvus_ba_set_x', ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     ('mvus_spline_eval', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p, c_double_p, c_int32_p]),
     ('mvus_spline_cov_eval', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p, c_double_p, c_int32_p]),
+    ('mvus_spline_eval_der', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int32,
+                                            c_double_p, c_int32_p]),
+    ('mvus_spline_kin_cov_eval', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p,
+                                                ctypes.c_int32, c_double_p, c_int32_p]),
+    ('mvus_spline_length', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p, c_double_p,
+                                          c_int32_p, c_double_p]),
     ('mvus_spline_lsq', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
     ('mvus_spline_smooth', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_double, c_int32_p, c_double_p, c_double_p,
                                           c_double_p, c_int32_p]),

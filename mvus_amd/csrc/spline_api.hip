@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "api_common.h"
@@ -125,6 +126,111 @@ int mvus_spline_cov_eval(int32_t device, int32_t S, const double* interval, cons
     MVUS_HIP(hipGetLastError());
     MVUS_HIP(hipMemcpyAsync(cov, dC, sizeof(double) * 9 * nt, hipMemcpyDeviceToHost, cb.st));
     MVUS_HIP(hipMemcpyAsync(which, dw, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipStreamSynchronize(cb.st));
+    return MVUS_OK;
+  });
+}
+
+// ---- kinematics: the three calls share mvus_spline_eval's arguments and its checks -------------------------------------------------------
+static bool kin_args_ok(const char* name, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots, const void* values, int64_t nt,
+                        const double* t, const void* out, const int32_t* which) {
+  if (S < 1 || !interval || !knot_offsets || !knots || !values || nt < 0 || (nt > 0 && (!t || !out || !which))) { g_create_error = std::string(name) + ": bad arguments"; return false; }
+  for (int s = 0; s < S; ++s)
+    if (knot_offsets[s + 1] - knot_offsets[s] < 8) { g_create_error = std::string(name) + ": a cubic spline needs at least 8 knots"; return false; }
+  return true;
+}
+// the splines on the device (coefs may be NULL: no coefficients uploaded); ctrl[s] receives the number of control points before spline s
+static SplineSet kin_upload(CallBuffers& cb, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots, const double* coefs,
+                            std::vector<long long>& ctrl) {
+  std::vector<long long> koff(knot_offsets, knot_offsets + S + 1), coff(S + 1, 0);
+  ctrl.assign(S + 1, 0);
+  for (int s = 0; s < S; ++s) { ctrl[s + 1] = ctrl[s] + (koff[s + 1] - koff[s] - 4); coff[s + 1] = 3 * ctrl[s + 1]; }
+  SplineSet sp;
+  sp.S = S;
+  sp.istart = cb.put(interval, (size_t)S); sp.iend = cb.put(interval + S, (size_t)S);
+  sp.knot_off = cb.put(koff.data(), koff.size()); sp.knots = cb.put(knots, (size_t)koff[S]);
+  sp.coef_off = coefs ? cb.put(coff.data(), coff.size()) : nullptr;
+  sp.coefs = coefs ? cb.put(coefs, (size_t)coff[S]) : nullptr;
+  return sp;
+}
+
+int mvus_spline_eval_der(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
+                         const double* coefs, int64_t nt, const double* t, int32_t nder, double* D, int32_t* which) {
+  if (!kin_args_ok("spline_eval_der", S, interval, knot_offsets, knots, coefs, nt, t, D, which)) return MVUS_E_INVALID;
+  if (nder < 0 || nder > 2) { g_create_error = "spline_eval_der: nder must be 0, 1 or 2"; return MVUS_E_INVALID; }
+  if (nt == 0) return MVUS_OK;
+  return stateless([&] {
+    CallBuffers cb;
+    cb.open(device);
+    std::vector<long long> ctrl;
+    const SplineSet sp = kin_upload(cb, S, interval, knot_offsets, knots, coefs, ctrl);
+    const size_t rows = 3 * (size_t)(nder + 1);
+    const double* dt = cb.put(t, (size_t)nt);
+    double* dD = cb.get<double>(rows * (size_t)nt);
+    int32_t* dw = cb.get<int32_t>((size_t)nt);
+    hipLaunchKernelGGL(k_spline_eval_der, fit_blocks(nt), dim3(256), 0, cb.st, sp, (long long)nt, dt, (int)nder, dD, dw);
+    MVUS_HIP(hipGetLastError());
+    MVUS_HIP(hipMemcpyAsync(D, dD, sizeof(double) * rows * nt, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipMemcpyAsync(which, dw, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipStreamSynchronize(cb.st));
+    return MVUS_OK;
+  });
+}
+
+int mvus_spline_kin_cov_eval(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
+                             const double* cov_band, int64_t nt, const double* t, int32_t nder, double* cov, int32_t* which) {
+  if (!kin_args_ok("spline_kin_cov_eval", S, interval, knot_offsets, knots, cov_band, nt, t, cov, which)) return MVUS_E_INVALID;
+  if (nder < 0 || nder > 2) { g_create_error = "spline_kin_cov_eval: nder must be 0, 1 or 2"; return MVUS_E_INVALID; }
+  if (nt == 0) return MVUS_OK;
+  return stateless([&] {
+    CallBuffers cb;
+    cb.open(device);
+    std::vector<long long> ctrl;
+    const SplineSet sp = kin_upload(cb, S, interval, knot_offsets, knots, nullptr, ctrl);
+    const long long* dctrl = cb.put(ctrl.data(), ctrl.size());
+    const double* dband = cb.put(cov_band, (size_t)ctrl[S] * 36);
+    const size_t dd = (size_t)kin_dim(nder) * kin_dim(nder);
+    const double* dt = cb.put(t, (size_t)nt);
+    double* dC = cb.get<double>(dd * (size_t)nt);
+    int32_t* dw = cb.get<int32_t>((size_t)nt);
+    if (nder == 0) hipLaunchKernelGGL(k_spline_kin_cov_eval<0>, fit_blocks(nt), dim3(256), 0, cb.st, sp, dctrl, dband, (long long)nt, dt, dC, dw);
+    else if (nder == 1) hipLaunchKernelGGL(k_spline_kin_cov_eval<1>, fit_blocks(nt), dim3(256), 0, cb.st, sp, dctrl, dband, (long long)nt, dt, dC, dw);
+    else hipLaunchKernelGGL(k_spline_kin_cov_eval<2>, fit_blocks(nt), dim3(256), 0, cb.st, sp, dctrl, dband, (long long)nt, dt, dC, dw);
+    MVUS_HIP(hipGetLastError());
+    MVUS_HIP(hipMemcpyAsync(cov, dC, sizeof(double) * dd * nt, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipMemcpyAsync(which, dw, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipStreamSynchronize(cb.st));
+    return MVUS_OK;
+  });
+}
+
+int mvus_spline_length(int32_t device, int32_t S, const double* interval, const int64_t* knot_offsets, const double* knots,
+                       const double* coefs, int64_t nt, const double* t, double* dist, int32_t* which, double* total) {
+  if (!kin_args_ok("spline_length", S, interval, knot_offsets, knots, coefs, nt, t, dist, which)) return MVUS_E_INVALID;
+  if (nt == 0 && !total) return MVUS_OK;
+  return stateless([&] {
+    CallBuffers cb;
+    cb.open(device);
+    std::vector<long long> ctrl;
+    const SplineSet sp = kin_upload(cb, S, interval, knot_offsets, knots, coefs, ctrl);
+    std::vector<long long> soff(S + 1, 0);                                 // spans (l = 3 .. n - 1) before spline s
+    for (int s = 0; s < S; ++s) soff[s + 1] = soff[s] + (ctrl[s + 1] - ctrl[s] - 3);
+    const long long* dsoff = cb.put(soff.data(), soff.size());
+    double* dlen = cb.get<double>((size_t)soff[S]);
+    double* dtot = cb.get<double>((size_t)S);
+    hipLaunchKernelGGL(k_span_length, fit_blocks(soff[S]), dim3(256), 0, cb.st, sp, dsoff, dlen);
+    hipLaunchKernelGGL(k_span_prefix, dim3((unsigned)S), dim3(64), 0, cb.st, (int)S, dsoff, dlen, dtot);
+    MVUS_HIP(hipGetLastError());
+    if (nt > 0) {
+      const double* dt = cb.put(t, (size_t)nt);
+      double* dd = cb.get<double>((size_t)nt);
+      int32_t* dw = cb.get<int32_t>((size_t)nt);
+      hipLaunchKernelGGL(k_spline_length, fit_blocks(nt), dim3(256), 0, cb.st, sp, dsoff, dlen, (long long)nt, dt, dd, dw);
+      MVUS_HIP(hipGetLastError());
+      MVUS_HIP(hipMemcpyAsync(dist, dd, sizeof(double) * nt, hipMemcpyDeviceToHost, cb.st));
+      MVUS_HIP(hipMemcpyAsync(which, dw, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, cb.st));
+    }
+    if (total) MVUS_HIP(hipMemcpyAsync(total, dtot, sizeof(double) * S, hipMemcpyDeviceToHost, cb.st));
     MVUS_HIP(hipStreamSynchronize(cb.st));
     return MVUS_OK;
   });

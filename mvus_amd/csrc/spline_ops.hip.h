@@ -8,9 +8,13 @@
 //                     adaptively inside its smooth_factor loop (common.py:224-270); that search stays on the host
 //                     (Scene.traj_to_spline), this is the refit on the knots it found -- scipy's make_lsq_spline is the oracle.
 //   k_spline_cov_eval the covariance of the same samples from the control points' band of mvus_ba_covariance (cov_spline_sample)
+//   k_spline_eval_der, k_spline_kin_cov_eval, k_span_length / k_span_prefix / k_spline_length
+//                     kinematics of the same samples (spline_kin_math.h): X, X', X''; the covariance of that state from the band; the
+//                     distance flown since the start of the interval
 #pragma once
 #include "ba_math.h"
 #include "ba_cov_math.h"
+#include "spline_kin_math.h"
 
 namespace mvus {
 
@@ -73,6 +77,134 @@ __global__ __launch_bounds__(256) void k_spline_cov_eval(SplineSet sp, const lon
   }
 #pragma unroll
   for (int e = 0; e < 9; ++e) cov[i * 9 + e] = o[e];
+}
+
+// ---- kinematics ------------------------------------------------------------------------------------------------------------------
+// interval of x as k_spline_eval finds it (closed at both ends), -1 outside
+__device__ __forceinline__ int spline_interval_of(const SplineSet& sp, double x) {
+  int lo = 0, hi = sp.S;
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (x >= sp.istart[mid]) lo = mid; else hi = mid; }
+  return x >= sp.istart[lo] && x <= sp.iend[lo] ? lo : -1;
+}
+
+// X, X', .., D^nder X per sample, D[(nder + 1)][3][nt]: one span search and one recurrence per lane; order 0 is k_spline_eval's sum
+__global__ __launch_bounds__(256) void k_spline_eval_der(SplineSet sp, long long nt, const double* __restrict__ t, int nder, double* __restrict__ D,
+                                                         int32_t* __restrict__ which) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= nt) return;
+  const double x = t[i];
+  const int s = spline_interval_of(sp, x);
+  which[i] = s;
+  double o[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (s >= 0) {
+    const double* k = sp.knots + sp.knot_off[s];
+    const int n = (int)(sp.knot_off[s + 1] - sp.knot_off[s]) - 4;
+    const int l = find_span(k, n, x);
+    double H[3][4];
+    bspline_basis_d2(k, l, x, H[0], H[1], H[2]);
+    const double* c = sp.coefs + sp.coef_off[s] + (l - 3);
+#pragma unroll
+    for (int v = 0; v < 3; ++v)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        o[3 * v + 0] = o[3 * v + 0] + c[q] * H[v][q]; o[3 * v + 1] = o[3 * v + 1] + c[n + q] * H[v][q]; o[3 * v + 2] = o[3 * v + 2] + c[2 * n + q] * H[v][q];
+      }
+  }
+#pragma unroll
+  for (int v = 0; v < 3; ++v)
+    if (v <= nder) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) D[(3 * v + d) * nt + i] = o[3 * v + d];
+    }
+}
+
+// Covariance of the state (X, .., D^NDER X) per sample, cov[nt][D][D] from band[N][4][3][3] (as k_spline_cov_eval): one lane per sample
+// computes the upper triangle (kin_state_cov_tri); a lane's matrix lies D * D * 8 bytes (648 for NDER = 2) from its neighbour's, so the
+// workgroup's triangles go through LDS ([entry][lane]: the lanes of a wavefront write one bank row) and its stretch of cov is written
+// in order, every entry and its mirror image from the same LDS word.  NaN outside every interval.
+template <int NDER>
+__global__ __launch_bounds__(256) void k_spline_kin_cov_eval(SplineSet sp, const long long* __restrict__ ctrl_off, const double* __restrict__ band, long long nt,
+                                                             const double* __restrict__ t, double* __restrict__ cov, int32_t* __restrict__ which) {
+  constexpr int D = kin_dim(NDER), T = kin_tri_count(NDER);
+  __shared__ double stage[T * 256];
+  const long long base = blockIdx.x * 256ll, i = base + threadIdx.x;
+  if (i < nt) {
+    const double x = t[i];
+    const int s = spline_interval_of(sp, x);
+    which[i] = s;
+    double tri[T];
+    if (s >= 0) {
+      const double* k = sp.knots + sp.knot_off[s];
+      const int n = (int)(sp.knot_off[s + 1] - sp.knot_off[s]) - 4;
+      const int l = find_span(k, n, x);
+      double H[12];
+      bspline_basis_d2(k, l, x, H, H + 4, H + 8);
+      kin_state_cov_tri<NDER>(H, band + (ctrl_off[s] + (l - 3)) * 36, tri);
+    } else {
+#pragma unroll
+      for (int e = 0; e < T; ++e) tri[e] = __builtin_nan("");
+    }
+#pragma unroll
+    for (int e = 0; e < T; ++e) stage[e * 256 + threadIdx.x] = tri[e];
+  }
+  __syncthreads();
+  const long long left = nt - base;
+  const int cnt = (int)(left < 256 ? left : 256) * (D * D);          // doubles this workgroup owns, contiguous from cov + base * D * D
+  double* out = cov + base * (D * D);
+  for (int e = threadIdx.x; e < cnt; e += 256) {
+    const int lane = e / (D * D), pq = e % (D * D), P = pq / D, Q = pq % D;
+    out[e] = stage[(P <= Q ? kin_tri(D, P, Q) : kin_tri(D, Q, P)) * 256 + lane];
+  }
+}
+
+// Path length, step 1: one lane per knot span (all splines one behind the other, span_off[s] = index of spline s' first span, n_s - 3 each):
+// the length of the span's part inside the interval
+__global__ __launch_bounds__(256) void k_span_length(SplineSet sp, const long long* __restrict__ span_off, double* __restrict__ len) {
+  const long long g = blockIdx.x * 256ll + threadIdx.x;
+  if (g >= span_off[sp.S]) return;
+  int lo = 0, hi = sp.S;                              // last spline whose first span <= g
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (g >= span_off[mid]) lo = mid; else hi = mid; }
+  const double* k = sp.knots + sp.knot_off[lo];
+  const int n = (int)(sp.knot_off[lo + 1] - sp.knot_off[lo]) - 4;
+  const int l = 3 + (int)(g - span_off[lo]);
+  len[g] = kin_span_part(k, n, sp.coefs + sp.coef_off[lo], l, sp.istart[lo], sp.iend[lo], sp.iend[lo]);
+}
+// step 2: exclusive prefix sum of a spline's span lengths, in place, and the interval's length.  One wavefront per spline loads 64 spans
+// at a time and every lane adds them up in the order of the spans (lane k's value broadcast at step k), keeping the total it saw before its
+// own span: prefix[j + 1] = prefix[j] + len[j] to the bit, total = prefix[count] -- one fixed order, no atomics
+__global__ __launch_bounds__(64) void k_span_prefix(int S, const long long* __restrict__ span_off, double* __restrict__ len, double* __restrict__ total) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const long long b = span_off[s], cnt = span_off[s + 1] - b;
+  double carry = 0.0;
+  for (long long j0 = 0; j0 < cnt; j0 += 64) {
+    const long long j = j0 + lane;
+    const double v = j < cnt ? len[b + j] : 0.0;
+    double before = 0.0;
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+      if (lane == k) before = carry;
+      carry = carry + __shfl(v, k, 64);
+    }
+    if (j < cnt) len[b + j] = before;
+  }
+  if (lane == 0) total[s] = carry;
+}
+// step 3: one lane per sample: the spans before its own (the prefix) plus the part of its own span up to the sample
+__global__ __launch_bounds__(256) void k_spline_length(SplineSet sp, const long long* __restrict__ span_off, const double* __restrict__ prefix, long long nt,
+                                                       const double* __restrict__ t, double* __restrict__ dist, int32_t* __restrict__ which) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= nt) return;
+  const double x = t[i];
+  const int s = spline_interval_of(sp, x);
+  which[i] = s;
+  double d = 0.0;
+  if (s >= 0) {
+    const double* k = sp.knots + sp.knot_off[s];
+    const int n = (int)(sp.knot_off[s + 1] - sp.knot_off[s]) - 4;
+    const int l = find_span(k, n, x);
+    d = prefix[span_off[s] + (l - 3)] + kin_span_part(k, n, sp.coefs + sp.coef_off[s], l, sp.istart[s], sp.iend[s], x);
+  }
+  dist[i] = d;
 }
 
 // ---- least squares on fixed knots ------------------------------------------------------------------------------------

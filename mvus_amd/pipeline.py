@@ -188,7 +188,8 @@ def evaluate_against_truth(flight, sc):
 def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output=True):
     """main.py:18-93 from the config.json at ``path`` (the reference's schema; ``create_scene``): every stage through
     ``StageTimer`` -- create_scene, cut_detection, init_alpha, time_shift, detection_to_global, init_traj(error=thres_Fmatix),
-    traj_to_spline, the incremental loop, spline_to_traj; ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true; ``align_gt`` when the config gives ground truth; the Scene pickled to
+    traj_to_spline, the incremental loop, spline_to_traj; ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true; ``Scene.kinematics`` (stage 'kinematics') when
+    ``settings['ba_kinematics']`` is true; ``align_gt`` when the config gives ground truth; the Scene pickled to
     ``settings['path_output']`` when ``output`` and that key is set.  Returns (Scene, StageTimer)."""
     from .reconstruction import common
     timer = timer or StageTimer()
@@ -206,6 +207,9 @@ def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output
         # settings['ba_covariance']: the covariance of the last BA's problem (all cameras of the sequence), carried by the pickle as flight.covariance
         timer.run('ba_covariance', flight.numCam, flight.ba_covariance, list(flight.sequence[:flight.numCam if flight.find_order else len(flight.sequence)]), rs=st['rolling_shutter'], motion_reg=st['motion_reg'],
                   motion_weights=st['motion_weights'], rs_bounds=st['rs_bounds'])
+    if flight.ba_kinematics_enabled():
+        # settings['ba_kinematics']: velocity, acceleration and distance flown at the stamps of the trajectory, with their 1-sigma when the covariance is there
+        timer.run('kinematics', flight.numCam, flight.kinematics, cov=flight.covariance if flight.ba_covariance_enabled() else None)
     if flight.gt:
         from .analysis.compare_gt import align_gt
         flight.out = timer.run('align_gt', flight.numCam, align_gt, flight, flight.gt['frequency'], flight.gt['filepath'], visualize=False)

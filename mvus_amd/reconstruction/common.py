@@ -42,6 +42,8 @@ Extra ``settings`` keys (all optional; a reference ``config.json`` has none of t
                (``Scene.ba_frozen_mask``).
 ``ba_covariance`` True: ``mvus_amd.pipeline.reconstruct_from_config`` calls ``Scene.ba_covariance`` after the last BA and the output pickle carries
                its dict (``Scene.covariance``).  DEFAULT False: nothing changes.  Needs a fixed gauge (``ba_gauge: 'anchor'`` or ``ba_freeze``).
+``ba_kinematics`` True: ``reconstruct_from_config`` calls ``Scene.kinematics`` after ``spline_to_traj`` (after ``Scene.ba_covariance``, with its band, when
+               ``ba_covariance`` is on too) and the output pickle carries its dict.  DEFAULT False: nothing changes.
 ``ba_deterministic`` accepted and ignored: the 'lm' solver's normal equations are assembled without floating-point atomics
                (one writer, one order of additions per entry) -- the same bits on every run by construction.
 ``opt_sync`` (reference key: False freezes alpha/beta), ``device``.
@@ -513,6 +515,7 @@ class Scene:
         self.ba_loss()                       # (validated with the rest: a bad ba_loss / ba_f_scale raises before any GPU call)
         self.ba_freeze()                     # (and ba_freeze / ba_gauge)
         self.ba_covariance_enabled()         # (and ba_covariance)
+        self.ba_kinematics_enabled()         # (and ba_kinematics)
         return solver, modes[jac]
 
     def ba_covariance_enabled(self):
@@ -522,6 +525,55 @@ class Scene:
         if not isinstance(v, (bool, np.bool_)):
             raise ValueError("settings['ba_covariance'] must be true or false, not %r" % (v,))
         return bool(v)
+
+    def ba_kinematics_enabled(self):
+        """settings['ba_kinematics'] validated (a bool; absent = False): host only."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        v = st.get('ba_kinematics', False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("settings['ba_kinematics'] must be true or false, not %r" % (v,))
+        return bool(v)
+
+    def kinematics(self, t=None, fps=None, cov=None):
+        """Velocity, acceleration, speed and distance flown along the trajectory splines at timestamps ``t`` (default: the stamps of
+        ``spline_to_traj``, ``self.traj[0]``), differentiated on the spline itself (``mvus_spline_eval_der``, ``mvus_spline_length``) instead
+        of differencing samples.  The spline parameter runs in frames of the reference camera; ``fps`` (default: that camera's) converts to
+        per-second values: velocity x fps, acceleration x fps^2, covariance blocks by the matching products; ``fps=1`` keeps per-frame units.
+        ``cov``: the dict ``ba_covariance`` returned, or its band [N, 4, 3, 3] -- then the 1-sigma of each (``mvus_spline_kin_cov_eval``); a
+        band that does not fit the current splines raises ValueError.  Stores and returns a data-only dict:
+          t, which (interval of each stamp, -1 outside: zeros / NaN there), fps,
+          pos [3, nt], vel [3, nt], acc [3, nt], speed [nt] = |vel|,
+          dist [nt] distance flown, continued over the intervals in order (an interval starts at the length of those before it; the gaps
+          count nothing), length [S] of each interval,
+          with ``cov``: state_cov [nt, 9, 9] of (pos, vel, acc), vel_std [nt, 3], acc_std [nt, 3], speed_std [nt] = sqrt(u^T Cov(vel) u),
+          u = vel / speed (NaN where the speed is 0).
+        The variance of ``dist`` needs covariances between control points further apart than the band holds; it is not given.
+        The dict is stored as ``self.kinematics`` -- on the instance it takes this method's place, so a later evaluation of the same Scene
+        goes through the class: ``Scene.kinematics(scene, ...)``."""
+        from .. import spline as _spline
+        tck, interval = self.spline['tck'], self.spline['int']
+        ts = np.asarray(self.traj[0] if t is None else t, dtype=np.float64)
+        fps = float(self.cameras[self.ref_cam].fps if fps is None else fps)
+        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
+        D, which = _spline.evaluate_der(tck, interval, ts, nder=2, device=device)
+        dist, _, length = _spline.path_length(tck, interval, ts, device=device)
+        before = np.concatenate(([0.0], np.cumsum(length)[:-1]))
+        dist = np.where(which >= 0, dist + before[np.maximum(which, 0)], 0.0)
+        vel, acc = D[1] * fps, D[2] * fps ** 2
+        out = {'t': ts.copy(), 'which': which, 'fps': fps, 'pos': D[0].copy(), 'vel': vel, 'acc': acc, 'speed': np.sqrt(np.sum(vel * vel, axis=0)),
+               'dist': dist, 'length': length}
+        if cov is not None:
+            band = np.asarray(cov['band'] if isinstance(cov, dict) else cov, dtype=np.float64)
+            state_cov, _ = _spline.kin_cov_evaluate(tck, interval, band, ts, nder=2, device=device)          # (checks the band's shape)
+            unit = np.repeat([1.0, fps, fps ** 2], 3)
+            state_cov = state_cov * np.outer(unit, unit)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                sd = np.sqrt(np.einsum('tii->ti', state_cov))
+                u = vel / out['speed']
+                speed_std = np.sqrt(np.einsum('it,tij,jt->t', u, state_cov[:, 3:6, 3:6], u))
+            out.update(state_cov=state_cov, vel_std=sd[:, 3:6].copy(), acc_std=sd[:, 6:9].copy(), speed_std=speed_std)
+        self.kinematics = out
+        return out
 
     def ba_param_names(self):
         """Names of the P parameters of one camera in x (Camera.P2vector order)."""

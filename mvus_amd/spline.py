@@ -1,6 +1,9 @@
 """Spline maintenance either side of BA on the GPU, through the C ABI:
 
 ``evaluate``   = the evaluation inside ``Scene.spline_to_traj`` (reference common.py:273-301; scipy ``splev``)
+``evaluate_der`` / ``kin_cov_evaluate`` / ``path_length`` = kinematics of the same samples: X, X', X'' (scipy ``splev(der=)``), the
+                 covariance of that state from the control points' band, the distance flown (``mvus_spline_eval_der``,
+                 ``mvus_spline_kin_cov_eval``, ``mvus_spline_length``)
 ``lsq_fit``    = least-squares coefficients on a fixed knot vector (the refit step of ``traj_to_spline`` once the knots are
                  placed; scipy ``make_lsq_spline``)
 ``smooth_fit``  = ``scipy.interpolate.splprep(X, u=t, s=s, k=3)``: FITPACK's adaptive knot placement and smoothing-parameter search
@@ -63,6 +66,68 @@ def cov_evaluate(tck, interval, band, t, device=0):
     if rc != 0:
         _err(lib, rc, 'mvus_spline_cov_eval')
     return cov, which
+
+
+def _spline_args(tck, interval, t):
+    """(interval, S, knot offsets, knots, t) as the stateless spline calls take them"""
+    interval = np.ascontiguousarray(np.asarray(interval, dtype=np.float64))
+    knots = [np.asarray(k[0], dtype=np.float64) for k in tck]
+    koff = np.concatenate(([0], np.cumsum([k.size for k in knots]))).astype(np.int64)
+    kn = np.ascontiguousarray(np.concatenate(knots))
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    if t.ndim != 1:
+        raise ValueError('Input timestamps must be a 1D array')
+    return interval, interval.shape[1], koff, kn, t
+
+
+def evaluate_der(tck, interval, t, nder=2, device=0):
+    """The points of ``evaluate`` with their first ``nder`` (0, 1 or 2) derivatives in the spline parameter: (D[nder + 1, 3, len(t)],
+    which[len(t)]), D[0] = ``evaluate``'s X to the bit, D[1] = X', D[2] = X''; 0 where which = -1.  ``mvus_spline_eval_der``."""
+    lib = _lib.load()
+    interval, S, koff, kn, t = _spline_args(tck, interval, t)
+    coefs = np.concatenate([np.ravel(np.asarray(k[1], dtype=np.float64)) for k in tck])
+    D = np.zeros((max(int(nder), 0) + 1, 3, t.size))
+    which = np.full(t.size, -1, dtype=np.int32)
+    rc = lib.mvus_spline_eval_der(int(device), int(S), _lib.dptr(interval), koff.ctypes.data_as(_lib.c_int64_p), _lib.dptr(kn), _lib.dptr(coefs),
+                                  t.size, _lib.dptr(t), int(nder), _lib.dptr(D), which.ctypes.data_as(_lib.c_int32_p))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_eval_der')
+    return D, which
+
+
+def kin_cov_evaluate(tck, interval, band, t, nder=2, device=0):
+    """Covariance of the state (X, X', .., D^nder X) at timestamps ``t`` from ``band`` [N, 4, 3, 3] (as ``cov_evaluate``):
+    (cov[len(t), D, D], which[len(t)]) with D = 3 (nder + 1), component 3 i + r = coordinate r of derivative i; exactly symmetric; NaN
+    where which = -1.  ``mvus_spline_kin_cov_eval``."""
+    lib = _lib.load()
+    interval, S, koff, kn, t = _spline_args(tck, interval, t)
+    band = np.ascontiguousarray(band, dtype=np.float64)
+    if band.shape != (int(koff[-1]) - 4 * S, 4, 3, 3):
+        raise ValueError('band has shape %s, expected (%d, 4, 3, 3)' % (band.shape, int(koff[-1]) - 4 * S))
+    D = 3 * (max(int(nder), 0) + 1)
+    cov = np.full((t.size, D, D), np.nan)
+    which = np.full(t.size, -1, dtype=np.int32)
+    rc = lib.mvus_spline_kin_cov_eval(int(device), int(S), _lib.dptr(interval), koff.ctypes.data_as(_lib.c_int64_p), _lib.dptr(kn), _lib.dptr(band),
+                                      t.size, _lib.dptr(t), int(nder), _lib.dptr(cov), which.ctypes.data_as(_lib.c_int32_p))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_kin_cov_eval')
+    return cov, which
+
+
+def path_length(tck, interval, t, device=0):
+    """Distance flown: (dist[len(t)], which[len(t)], total[S]) -- ``dist`` the length of the curve from the start of the timestamp's interval
+    to the timestamp (0 where which = -1), ``total`` the length of each interval.  ``mvus_spline_length``."""
+    lib = _lib.load()
+    interval, S, koff, kn, t = _spline_args(tck, interval, t)
+    coefs = np.concatenate([np.ravel(np.asarray(k[1], dtype=np.float64)) for k in tck])
+    dist = np.zeros(t.size)
+    which = np.full(t.size, -1, dtype=np.int32)
+    total = np.zeros(S)
+    rc = lib.mvus_spline_length(int(device), int(S), _lib.dptr(interval), koff.ctypes.data_as(_lib.c_int64_p), _lib.dptr(kn), _lib.dptr(coefs),
+                                t.size, _lib.dptr(t), _lib.dptr(dist), which.ctypes.data_as(_lib.c_int32_p), _lib.dptr(total))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_length')
+    return dist, which, total
 
 
 def lsq_fit(knots, t, X, device=0):
