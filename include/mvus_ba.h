@@ -427,7 +427,9 @@ int mvus_spline_length(int32_t device, int32_t S, const double* interval, const 
 /* Least-squares cubic spline on a FIXED knot vector (num_knots = n + 4, first/last four equal): coefs[3*n] (cx cy cz)
  * minimising sum_i |X(t_i) - X_i|^2 over the m data points t[m], X[3*m] (x(m) y(m) z(m)), t inside [knots[3], knots[n]].
  * The coefficient refit of Scene.traj_to_spline (common.py:224-270) once FITPACK's adaptive search has placed the knots (that
- * search stays on the host); equals scipy.interpolate.make_lsq_spline.  MVUS_E_NUMERIC when a coefficient has no data. */
+ * search stays on the host); equals scipy.interpolate.make_lsq_spline.  MVUS_E_NUMERIC when the data do not
+ * determine every coefficient (Schoenberg-Whitney violated: m < n, a coefficient without data, a pivot of the normal equations
+ * below 1e-12 of its diagonal entry). */
 int mvus_spline_lsq(int32_t device, int32_t num_knots, const double* knots, int64_t m, const double* t, const double* X, double* coefs);
 
 /* The smoothing-spline fit inside Scene.traj_to_spline (common.py:247, :267): scipy.interpolate.splprep(X, u=u, s=s, k=3), i.e.

@@ -241,6 +241,7 @@ int mvus_spline_lsq(int32_t device, int32_t num_knots, const double* knots, int6
   if (num_knots < 8 || !knots || m < 1 || !t || !X || !coefs) { g_create_error = "spline_lsq: bad arguments"; return MVUS_E_INVALID; }
   for (int k = 1; k < num_knots; ++k) if (knots[k] < knots[k - 1]) { g_create_error = "spline_lsq: knot vector must be non-decreasing"; return MVUS_E_INVALID; }
   for (int64_t i = 0; i < m; ++i) if (!(t[i] >= knots[3] && t[i] <= knots[n])) { g_create_error = "spline_lsq: data outside the knot interval"; return MVUS_E_INVALID; }
+  if (m < n) { g_create_error = "spline_lsq: fewer samples than coefficients (Schoenberg-Whitney violated)"; return MVUS_E_NUMERIC; }
   return stateless([&] {
     CallBuffers cb;
     cb.open(device);
@@ -260,7 +261,7 @@ int mvus_spline_lsq(int32_t device, int32_t num_knots, const double* knots, int6
     MVUS_HIP(hipMemcpyAsync(coefs, rhs, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, cb.st));
     MVUS_HIP(hipMemcpyAsync(&fh, fail, sizeof(int), hipMemcpyDeviceToHost, cb.st));
     MVUS_HIP(hipStreamSynchronize(cb.st));
-    if (fh) { g_create_error = "spline_lsq: the normal equations are not positive definite (a coefficient without data: Schoenberg-Whitney violated)"; return MVUS_E_NUMERIC; }
+    if (fh) { g_create_error = "spline_lsq: the normal equations are not positive definite to working precision (the data do not determine every coefficient: Schoenberg-Whitney violated)"; return MVUS_E_NUMERIC; }
     return MVUS_OK;
   });
 }

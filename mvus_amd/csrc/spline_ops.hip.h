@@ -228,7 +228,12 @@ __global__ __launch_bounds__(256) void k_lsq_accumulate(const double* __restrict
 }
 
 // banded Cholesky G = L L^T (L keeps the band) and the three solves, one wavefront: lanes 0..2 carry the three right-hand
-// sides through the substitutions, the factorisation itself is a 4-wide recurrence done redundantly by every lane
+// sides through the substitutions, the factorisation itself is a 4-wide recurrence done redundantly by every lane.
+// A pivot that is not above kLsqPivotTol times its diagonal entry of G fails the fit: the entry is a sum of m squares accumulated in
+// any order, so the pivot carries an error of about sqrt(m) eps times it (7e-13 at m = 1e7) and a smaller one cannot be told from the
+// zero of a rank-deficient system (Schoenberg-Whitney violated although every coefficient has data) -- whose rounding residue is
+// positive as often as not and used to pass.  A full-rank system with such a pivot would have no correct digit left either.
+constexpr double kLsqPivotTol = 1e-12;
 __global__ __launch_bounds__(64) void k_lsq_solve(int n, double* __restrict__ G, double* __restrict__ rhs, int* __restrict__ fail) {
   const int lane = threadIdx.x;
   // factorise in place: L(j, j-w) in G[4j + w]
@@ -250,10 +255,11 @@ __global__ __launch_bounds__(64) void k_lsq_solve(int n, double* __restrict__ G,
       }
       row[w] = v / G[4 * k];
     }
+    const double diag = row[0];
     double d = row[0];
 #pragma unroll
     for (int u = 1; u <= 3; ++u) if (j - u >= 0) d -= row[u] * row[u];
-    if (!(d > 0.0)) { if (lane == 0) fail[0] = 1; d = 1.0; }
+    if (!(d > kLsqPivotTol * diag)) { if (lane == 0) fail[0] = 1; d = 1.0; }
     row[0] = sqrt(d);
     __syncthreads();                                 // every lane computed the same row; one writes it
     if (lane == 0) {

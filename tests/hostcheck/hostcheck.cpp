@@ -102,6 +102,23 @@ extern "C" int hostcheck_pnp_point_normal(const double* K, const double* d, cons
 }
 extern "C" void hostcheck_pnp_sample6(unsigned long long seed, int h, long long N, long long* idx) { pnp_sample6(seed, h, N, idx); }
 extern "C" void hostcheck_rotation_to_rvec(const double* R, double* r) { rotation_to_rvec(R, r); }
+// k_pnp_normalise for a pixel array: uv, xn: [2][N]; Kd = fx fy cx cy k1 k2 p1 p2 k3
+extern "C" void hostcheck_undistort5(long long N, const double* uv, const double* Kd, double* xn) {
+  for (long long i = 0; i < N; ++i) {
+    double xo, yo;
+    undistort5<false>((uv[i] - Kd[2]) / Kd[0], (uv[N + i] - Kd[3]) / Kd[1], Kd + 4, xo, yo, nullptr, nullptr);
+    xn[i] = xo; xn[N + i] = yo;
+  }
+}
+// k_pnp_score / k_pnp_mask for one pose: squared pixel error per point, -1 where the point is not in front.  X: [3][N]; uv, e2: [2][N], [N]
+extern "C" void hostcheck_pnp_sqerr(long long N, const double* X, const double* uv, const double* Kd, const double* R, const double* t, double* e2) {
+  for (long long i = 0; i < N; ++i) {
+    const double Xi[3] = {X[i], X[N + i], X[2 * N + i]};
+    double u, v;
+    e2[i] = -1.0;
+    if (pnp_project(Kd, Kd + 4, R, t, Xi, u, v)) { const double du = u - uv[i], dv = v - uv[N + i]; e2[i] = du * du + dv * dv; }
+  }
+}
 
 // host build of the two-view math (mvus_amd/csrc/epipolar.hip.h)
 extern "C" int hostcheck_fm_cubic_roots(const double* c /* c3 c2 c1 c0 */, double* r) { return fm_cubic_roots(c[0], c[1], c[2], c[3], r); }

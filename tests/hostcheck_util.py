@@ -55,6 +55,8 @@ def load():
     lib.hostcheck_pnp_point_normal.argtypes = [_lib.c_double_p] * 5 + [ctypes.c_double, ctypes.c_double, _lib.c_double_p]
     lib.hostcheck_pnp_sample6.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_longlong, _lib.c_int64_p]
     lib.hostcheck_rotation_to_rvec.argtypes = [_lib.c_double_p, _lib.c_double_p]
+    lib.hostcheck_undistort5.argtypes = [ctypes.c_longlong] + [_lib.c_double_p] * 3
+    lib.hostcheck_pnp_sqerr.argtypes = [ctypes.c_longlong] + [_lib.c_double_p] * 6
     lib.hostcheck_fm_cubic_roots.argtypes = [_lib.c_double_p, _lib.c_double_p]
     lib.hostcheck_fm_seven_point.argtypes = [_lib.c_double_p, _lib.c_double_p]
     lib.hostcheck_fm_error.argtypes = [ctypes.c_longlong] + [_lib.c_double_p] * 4
