@@ -147,7 +147,7 @@ void mvus_default_opts(mvus_solve_opts* opts);
  * sizeof(mvus_result), sizeof(mvus_problem) as this library was compiled (any pointer may be NULL) and returns MVUS_ABI_VERSION.  A
  * binding asserts these against its own struct definitions at load time -- mvus_solve_opts has grown over the rounds (lm_lambda_min,
  * lm_trust_radius) and a stale stub would otherwise hand the library a short buffer.  The version is raised whenever a struct or an
- * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance) does not raise
+ * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance, mvus_ba_set_position_priors) does not raise
  * it -- a binding that needs one finds it missing at load time.  Stateless, no device is touched.  No reference counterpart (the reference has no FFI). */
 #define MVUS_ABI_VERSION 8
 int32_t mvus_abi_sizes(int32_t* solve_opts_size, int32_t* result_size, int32_t* problem_size);
@@ -283,6 +283,37 @@ int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* w
  * above: never solved unmasked.  mvus_ba_num_frozen: the number of held unknowns (0 = no mask). */
 int mvus_ba_set_frozen(mvus_ba* h, const uint8_t* frozen, int64_t count);
 int64_t mvus_ba_num_frozen(const mvus_ba* h);
+
+/* Position priors on the trajectory (ba_prior.hip.h; no reference counterpart: the reference compares a GPS / RTK log with the result
+ * afterwards, analysis/compare_gt.py).  Prior k is a surveyed position p_k at time t_k with weights w_k = 1 / sigma_k per axis; it adds
+ * the three rows  r = w_k (.) (S(t_k) - p_k)  to the least-squares problem, S the cubic spline of the unknowns.  t_k is on the spline's
+ * own timeline (the reference camera's frame clock) and is a constant, not an unknown.  A weight of 0 leaves that axis out.  Three
+ * priors that are not collinear fix the seven freedoms of the similarity gauge: the solution, and its covariance, are then in the
+ * surveyed frame and in its unit, with no anchor.
+ *   t[K], P[3K] = x(K) y(K) z(K), w[3K] in the same layout, in any order (the library sorts by (t, input order)); K = 0 or a NULL array
+ *   clears the priors.  A prior is ACTIVE when start <= t_k <= end for some interval of the spline, both ends closed (at t_k = end the
+ *   basis is the right-end value, as splev gives it); the others contribute nothing and are only counted.
+ * State of the handle, as the loss and the frozen mask are: in force for every later mvus_ba_solve (MVUS_SOLVER_LM_SCHUR, every Jacobian
+ * mode) / mvus_ba_normal_equations / mvus_ba_lm_step / mvus_ba_covariance until set again, kept over mvus_ba_remove_outliers.  There
+ *   cost and initial_cost of mvus_result += 0.5 sum r^2;  g and the band of the normal equations gain  h_a w^2 (S - p)  and
+ *   h_a h_b diag(w^2)  on the four control points of the prior's knot span (h its four B-spline weights); the camera blocks, the camera
+ *   gradient and the cross block are untouched and the band is not widened;  the covariance's dof counts one row per active (prior, axis)
+ *   with w > 0.
+ * The rows are plain L2: a robust loss in force reweights detection and motion rows only.  Everything about error_BA itself (residual,
+ * Jacobian, J v, J^T u, motion rows, outlier masks, mvus_ba_robust_cost, f_out of a solve: 2M + T rows) stays raw.  Setting or clearing
+ * drops what an earlier LM solve carried over (cost, normal equations, the speculative linearisation) as mvus_ba_set_loss does, and leaves
+ * the damping history alone; a handle without active priors runs exactly the kernels it ran before this entry point existed.
+ * MVUS_E_INVALID: K < 0 or K > 2^28, a non-finite t, P or w, a negative weight.  MVUS_E_UNSUPPORTED: priors on a sharded handle ("sharded" in the
+ * message; set_allreduce / set_rccl / set_time_shard, here or -- when the route is installed afterwards -- from the calls above), and
+ * mvus_ba_solve with MVUS_SOLVER_TRF_LSMR while a prior is active ("TRF_LSMR" in the message): never solved with the priors dropped.
+ * Not offered: a time offset of the position log as an unknown, full 3 x 3 prior covariances.
+ * mvus_ba_num_position_priors: K as set; *active_out (may be NULL) the active ones.
+ * mvus_ba_position_prior_cost: 0.5 sum r^2 at x and, when r_out is not NULL, r[3K] in the CALLER's order and layout, NaN for inactive
+ * priors (inspection hook; one rank).  x is evaluated in a buffer of its own: the held Jacobian, its point, f and the blocks of the last
+ * mvus_ba_normal_equations stay as they are. */
+int mvus_ba_set_position_priors(mvus_ba* h, int64_t K, const double* t, const double* P, const double* w);
+int64_t mvus_ba_num_position_priors(const mvus_ba* h, int64_t* active_out);
+int mvus_ba_position_prior_cost(mvus_ba* h, const double* x, double* cost_out, double* r_out);
 
 /* Covariance of the estimate at x (ba_cov.hip.h; no reference counterpart: scipy's least_squares returns none either).  With the loss and the
  * frozen mask in force, H is the matrix mvus_ba_normal_equations exports at x -- J^T J, or scipy's J^T diag(s^2) J under a robust loss (the

@@ -86,6 +86,9 @@ API = [
     ('mvus_ba_set_loss', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
     ('mvus_ba_set_frozen', ctypes.c_int, [ctypes.c_void_p, c_uint8_p, ctypes.c_int64]),
     ('mvus_ba_num_frozen', ctypes.c_int64, [ctypes.c_void_p]),
+    ('mvus_ba_set_position_priors', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
+    ('mvus_ba_num_position_priors', ctypes.c_int64, [ctypes.c_void_p, c_int64_p]),
+    ('mvus_ba_position_prior_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
     ('mvus_ba_robust_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
     ('mvus_ba_covariance', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_double_p, c_double_p, c_uint8_p, c_double_p, c_int64_p]),
     ('mvus_ba_covariance_stage_ms', ctypes.c_int32, [ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32]),

@@ -26,6 +26,26 @@ def loss_code(loss):
     return int(loss)
 
 
+def position_prior_arrays(t, P, sigma):
+    """(t (K,), P (3, K), sigma scalar | (3,) | (3, K)) -> contiguous float64 (t, P, w) with w = 1 / sigma (0 for an infinite sigma).
+    Shapes, NaN and non-positive sigma raise ValueError here; the library checks the numbers again."""
+    t = np.ascontiguousarray(t, dtype=np.float64).ravel()
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    if P.shape != (3, t.size):
+        raise ValueError('position priors: P has shape %s, expected (3, %d)' % (P.shape, t.size))
+    s = np.asarray(sigma, dtype=np.float64)
+    if s.ndim == 1 and s.shape == (3,):
+        s = s[:, None]
+    elif s.ndim not in (0, 2) or (s.ndim == 2 and s.shape != (3, t.size)):
+        raise ValueError('position priors: sigma has shape %s, expected a scalar, (3,) or (3, %d)' % (s.shape, t.size))
+    s = np.broadcast_to(s, (3, t.size))
+    if np.any(np.isnan(s)) or np.any(s <= 0):
+        raise ValueError('position priors: sigma must be positive (np.inf leaves an axis out)')
+    with np.errstate(divide='ignore'):
+        w = np.ascontiguousarray(np.where(np.isinf(s), 0.0, 1.0 / s))
+    return t, P, w
+
+
 class UnsupportedBySolver(RuntimeError):
     """MVUS_E_UNSUPPORTED: the problem is outside what the chosen solver handles (see include/mvus_ba.h); the other solver has no such limit."""
 
@@ -259,6 +279,36 @@ class BAHandle:
     @property
     def num_frozen(self):
         return int(self.lib.mvus_ba_num_frozen(self.h))
+
+    def set_position_priors(self, t, P, sigma):
+        """Surveyed positions as observations (mvus_ba_set_position_priors): ``t`` (K,) on the spline's timeline, ``P`` (3, K), ``sigma`` the
+        1-sigma of a position as a scalar, per axis (3,) or per prior and axis (3, K); ``np.inf`` leaves that axis out (weight 0).  Each
+        prior adds the rows (S(t_k) - p_k) / sigma to every later LM solve / normal_equations / lm_step / covariance on the handle, kept
+        over remove_outliers.  ``t = None`` (or K = 0) clears them.  Priors outside every interval of the spline are inactive."""
+        if t is None or np.size(t) == 0:
+            self._check(self.lib.mvus_ba_set_position_priors(self.h, 0, None, None, None), 'mvus_ba_set_position_priors')
+            return
+        t, P, w = position_prior_arrays(t, P, sigma)
+        self._check(self.lib.mvus_ba_set_position_priors(self.h, t.size, _lib.dptr(t), _lib.dptr(P), _lib.dptr(w)), 'mvus_ba_set_position_priors')
+
+    @property
+    def num_position_priors(self):
+        return int(self.lib.mvus_ba_num_position_priors(self.h, None))
+
+    @property
+    def num_active_position_priors(self):
+        a = ctypes.c_int64(0)
+        self.lib.mvus_ba_num_position_priors(self.h, ctypes.byref(a))
+        return int(a.value)
+
+    def position_prior_cost(self, x, rows=False):
+        """0.5 sum r^2 of the position priors at x; with ``rows`` also r (3, K) in the order the priors were given, NaN for inactive ones."""
+        x = self._x(x, self.n)
+        cost = ctypes.c_double(0.0)
+        r = np.empty((3, self.num_position_priors)) if rows else None
+        self._check(self.lib.mvus_ba_position_prior_cost(self.h, _lib.dptr(x), ctypes.byref(cost), _lib.dptr(r) if rows else None),
+                    'mvus_ba_position_prior_cost')
+        return (cost.value, r) if rows else cost.value
 
     def robust_cost(self, x, weights=False):
         """0.5 f_scale^2 sum rho((f_i / f_scale)^2) at x under the loss in force; with ``weights`` also rho' of every row of f

@@ -20,6 +20,7 @@
 #include "ba_solver.h"
 #include "ba_switches.h"
 #include "ba_schur_hip.hip.h"
+#include "ba_prior.hip.h"
 #include "ba_schur_host.hip.h"
 #include "ba_cov.hip.h"
 
@@ -46,6 +47,7 @@ struct HipBackend {
   int32_t* rspan = nullptr;
   const double* rspan_for = nullptr;
   bool has_pattern = false, has_jacobian = false;
+  const double* jac_x = nullptr;      // device x the held Jacobian was evaluated at (the priors' pass behind an assembly from J needs the point)
   bool held_analytic_at_xcur = false; // the held Jacobian is the analytic one of x_cur (mvus_ba_residual_jacobian): its normal equations can be formed by the fused window-major assembly
   bool det_assembly = false;          // mvus_ba_set_deterministic (kept for the ABI: the window-major assembly is deterministic by construction)
   bool pattern_uploaded = false;     // the caller supplied the reference's pattern (mvus_ba_upload_pattern): solve keeps it
@@ -152,6 +154,7 @@ struct HipBackend {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     for (void* p : owned) (void)hipFree(p);
+    for (void* p : prior_owned) (void)hipFree(p);
     for (auto& kv : pool_size) (void)hipFree(kv.first);
     if (scal_host) (void)hipHostFree(scal_host);
     if (fetch_ev) (void)hipEventDestroy(fetch_ev);
@@ -468,7 +471,7 @@ struct HipBackend {
       }
     }
     MVUS_HIP(hipGetLastError());
-    if (jac) has_jacobian = true;
+    if (jac) { has_jacobian = true; jac_x = x; }
   }
   void residual(const double* x, double* f) { eval(x, f, false, 0); }
   // f = f(x) and out = |f|^2 (summed over the ranks): on one rank the residual kernels leave their workgroups' sums of squares
@@ -537,13 +540,90 @@ struct HipBackend {
     with_flag(hp.calib, [&](auto calib) { hipLaunchKernelGGL(k_freeze_jacobian<calib() ? 30 : 21>, dim3(dp.n_chunks), dim3(kThreads), 0, stream, dp, (const uint8_t*)frozen_slot, J); });
     MVUS_HIP(hipGetLastError());
   }
+  // Position priors on the trajectory (mvus_ba_set_position_priors, ba_prior.hip.h), state of the handle like the loss and the mask, kept
+  // over remove_outliers (they hang on the control points, which outlier removal leaves alone).  prior.K counts what the caller set,
+  // prior_active those whose time lies in an interval: with prior_active = 0 no kernel, argument or branch on the device differs from a
+  // handle that never had any.
+  PriorView prior{};
+  std::vector<void*> prior_owned;
+  std::vector<int64_t> prior_perm;          // sorted position -> the caller's index
+  int prior_active = 0;
+  uint64_t prior_gen = 0, prior_sets = 0;   // prior_gen names the set in force (HipSchur::assemble_held: which priors held blocks carry)
+  int64_t prior_rows = 0;                   // active (prior, axis) pairs with w > 0: the rows the covariance's degrees of freedom count
+  int prior_blocks() const { return prior_active > 0 ? (int)std::min<int64_t>(2048, ((int64_t)prior.K + kThreads - 1) / kThreads) : 0; }
+  void clear_priors() {
+    if (!prior_owned.empty()) MVUS_HIP(hipStreamSynchronize(stream));
+    for (void* p : prior_owned) (void)hipFree(p);
+    prior_owned.clear(); prior_perm.clear();
+    prior = PriorView{}; prior_active = 0; prior_rows = 0;
+  }
+  template <class T>
+  T* prior_upload(const std::vector<T>& v) {
+    void* p = nullptr;
+    MVUS_HIP(hipMalloc(&p, std::max<size_t>(v.size(), 1) * sizeof(T)));
+    prior_owned.push_back(p);
+    if (!v.empty()) MVUS_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+    return static_cast<T*>(p);
+  }
+  // t[K], P[3K], w[3K] in the caller's order (validated): sorted by (t, input order), span and weights by k_prior_setup, then the rows
+  // per control point on the host from the spans it found
+  void set_priors(int64_t K, const double* t, const double* P, const double* w) {
+    if (K <= 0) { clear_priors(); return; }
+    std::vector<int64_t> perm((size_t)K);
+    for (int64_t k = 0; k < K; ++k) perm[(size_t)k] = k;
+    std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return t[a] < t[b]; });
+    std::vector<double> ts((size_t)K), ps((size_t)3 * K), ws((size_t)3 * K);
+    for (int64_t k = 0; k < K; ++k) {
+      ts[(size_t)k] = t[perm[(size_t)k]];
+      for (int d = 0; d < 3; ++d) { ps[(size_t)(d * K + k)] = P[d * K + perm[(size_t)k]]; ws[(size_t)(d * K + k)] = w[d * K + perm[(size_t)k]]; }
+    }
+    clear_priors();
+    std::vector<int32_t> ctrl((size_t)K, -1);
+    const std::vector<double> hz((size_t)4 * K, 0.0);      // (pageable sources of asynchronous copies: alive until the synchronisation below)
+    try {
+      prior.K = (int)K;
+      prior.t = prior_upload(ts); prior.p = prior_upload(ps); prior.w = prior_upload(ws);
+      prior.ctrl = prior_upload(ctrl); prior.h = prior_upload(hz);
+      hipLaunchKernelGGL(k_prior_setup, dim3((unsigned)((K + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, dp.sp, prior);
+      MVUS_HIP(hipGetLastError());
+      MVUS_HIP(hipMemcpyAsync(ctrl.data(), prior.ctrl, sizeof(int32_t) * K, hipMemcpyDeviceToHost, stream));
+      MVUS_HIP(hipStreamSynchronize(stream));
+      const int N = hp.N;
+      std::vector<int32_t> lo((size_t)std::max(N, 1), 0), hi((size_t)std::max(N, 1), 0);
+      int active = 0;
+      int64_t rows = 0;
+      for (int64_t k = 0; k < K; ++k) {
+        const int c0 = ctrl[(size_t)k];
+        if (c0 < 0) continue;
+        if (c0 + 3 >= N) throw HipError{"set_position_priors: a knot span outside the control points (internal error)"};
+        ++active;
+        for (int d = 0; d < 3; ++d) if (ws[(size_t)(d * K + k)] > 0.0) ++rows;
+        for (int g = c0; g <= c0 + 3; ++g) {
+          if (hi[(size_t)g] == 0) lo[(size_t)g] = (int32_t)k;
+          hi[(size_t)g] = (int32_t)k + 1;
+        }
+      }
+      prior.row_lo = prior_upload(lo); prior.row_hi = prior_upload(hi);
+      MVUS_HIP(hipStreamSynchronize(stream));
+      prior_perm = perm; prior_active = active; prior_rows = rows; prior_gen = ++prior_sets;
+    } catch (...) { clear_priors(); throw; }
+  }
+  // behind an assembly at x (HipSchur::assemble): the priors' blocks are added to the spline gradient and the band
+  void prior_normal_equations(const NEView& ne, const double* x) {
+    if (x == nullptr || ne.W < 4 || ne.row0 != 0 || ne.N != hp.N) throw HipError{"position priors: the assembly has no point, or is not the whole spline block (internal error)"};
+    constexpr int kWaves = kThreads / 64;
+    hipLaunchKernelGGL(k_prior_ne, dim3((unsigned)((ne.N + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, dp, prior, x, ne);
+    MVUS_HIP(hipGetLastError());
+  }
   // clr / clr_len: storage to zero beside the evaluation (HipSchur's normal-equation blocks); returns false if it was not done
-  bool residual_sq(const double* x, double* f, double* out, double* clr = nullptr, int64_t clr_len = 0) {
+  // with_priors: the position priors' rows are part of the sum (every cost the solver and the covariance use; mvus_ba_robust_cost stays raw)
+  bool residual_sq(const double* x, double* f, double* out, double* clr = nullptr, int64_t clr_len = 0, bool with_priors = true) {
     // (observation shards off the root rank: the replicated motion rows are rows of zeros there -- the general path)
     if (allreduce && hp.T > 0 && !(is_root || tshard.on)) { residual(x, f); dot_m_into(f, f, out); return false; }
     RoctxRange range("mvus residual");
     const int mb = hp.T > 0 ? (int)((hp.T + kThreads - 1) / kThreads) : 0;
-    const size_t need = (size_t)dp.n_chunks + mb + 1;
+    const int pb = with_priors ? prior_blocks() : 0;
+    const size_t need = (size_t)dp.n_chunks + mb + pb + 1;
     const bool host_sum = scal_direct() && out >= scal_out() && out < scal_out() + 16 && !sw.sq_device_sum;
     const int set = (out == lm_scalars()) ? 0 : 1;
     double* sq_part = this->sq_part;
@@ -573,8 +653,9 @@ struct HipBackend {
     }
     if (mb > 0 && robust()) hipLaunchKernelGGL((k_motion<false, true>), dim3(mb), dim3(kThreads), 0, stream, dp, x, f + 2 * hp.M, mJ, mctrl, 0, sq_part + dp.n_chunks, loss);
     else if (mb > 0) hipLaunchKernelGGL(k_motion<false>, dim3(mb), dim3(kThreads), 0, stream, dp, x, f + 2 * hp.M, mJ, mctrl, 0, sq_part + dp.n_chunks);
-    if (host_sum) { sq_pend[set].slot = out - scal_out(); sq_pend[set].n = dp.n_chunks + mb; }      // added up by fetch()
-    else if (dp.n_chunks + mb > 0) hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kThreads), 0, stream, dp.n_chunks + mb, sq_part, out);
+    if (pb > 0) hipLaunchKernelGGL(k_prior_cost, dim3(pb), dim3(kThreads), 0, stream, dp, prior, x, sq_part + dp.n_chunks + mb, (double*)nullptr);
+    if (host_sum) { sq_pend[set].slot = out - scal_out(); sq_pend[set].n = dp.n_chunks + mb + pb; }      // added up by fetch()
+    else if (dp.n_chunks + mb + pb > 0) hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kThreads), 0, stream, dp.n_chunks + mb + pb, sq_part, out);
     else MVUS_HIP(hipMemsetAsync(out, 0, sizeof(double), stream));
     reduce(out, 1);                  // (sharded: the workgroups' partial sums replace a pass of k_dot_partial over f; the ranks' sums are added here)
     MVUS_HIP(hipGetLastError());
@@ -617,7 +698,7 @@ struct HipBackend {
       if (is_root) hipLaunchKernelGGL(k_fd_fill_motion, dim3((hp.T + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, dp, (long long)hp.m, f, fd_F, fd_dx, fd_groups, mJ, mctrl);
     }
     MVUS_HIP(hipGetLastError());
-    has_jacobian = true;
+    has_jacobian = true; jac_x = x;
   }
 
   // Scene.remove_outliers on the resident data: mask at x, stable compaction, new launch tables.
@@ -870,6 +951,13 @@ struct mvus_ba {
 static bool frozen_on_shards(HipBackend& be, const char* who) {
   if (be.frozen_count <= 0 || !(be.allreduce || be.tshard.on)) return false;
   be.err = std::string(who) + ": frozen parameters (mvus_ba_set_frozen) are not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard)";
+  return true;
+}
+
+// the same for position priors
+static bool priors_on_shards(HipBackend& be, const char* who) {
+  if (be.prior.K <= 0 || !(be.allreduce || be.tshard.on)) return false;
+  be.err = std::string(who) + ": position priors (mvus_ba_set_position_priors) are not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard)";
   return true;
 }
 
@@ -1206,7 +1294,7 @@ int mvus_ba_jtu(mvus_ba* h, const double* u, double* z) {
 
 int mvus_ba_normal_equations(mvus_ba* h, double* g, double* JtJ_cam, double* band, double* cross, int32_t* W_out) {
   return guarded(h, [&] {
-    if (frozen_on_shards(h->be, "normal_equations")) return MVUS_E_UNSUPPORTED;
+    if (frozen_on_shards(h->be, "normal_equations") || priors_on_shards(h->be, "normal_equations")) return MVUS_E_UNSUPPORTED;
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(h->be));
     h->schur->carry_held();
     return schur_export(h->be, *h->schur, g, JtJ_cam, band, cross, W_out);
@@ -1256,13 +1344,73 @@ int mvus_ba_set_frozen(mvus_ba* h, const uint8_t* frozen, int64_t count) {
 
 int64_t mvus_ba_num_frozen(const mvus_ba* h) { return h ? h->be.frozen_count : -1; }
 
+int mvus_ba_set_position_priors(mvus_ba* h, int64_t K, const double* t, const double* P, const double* w) {
+  return guarded(h, [&] {
+    HipBackend& be = h->be;
+    if (K < 0) { be.err = "set_position_priors: K < 0"; return MVUS_E_INVALID; }
+    if (K > (1ll << 28)) { be.err = "set_position_priors: more than 2^28 priors"; return MVUS_E_INVALID; }      // (4 K and 3 K stay inside int in the kernels' indices)
+    if (t == nullptr || P == nullptr || w == nullptr) K = 0;
+    for (int64_t k = 0; k < K; ++k)
+      if (!std::isfinite(t[k])) { be.err = "set_position_priors: t[" + std::to_string(k) + "] is not finite"; return MVUS_E_INVALID; }
+    for (int64_t k = 0; k < 3 * K; ++k) {
+      if (!std::isfinite(P[k])) { be.err = "set_position_priors: P[" + std::to_string(k) + "] is not finite"; return MVUS_E_INVALID; }
+      if (!std::isfinite(w[k]) || w[k] < 0.0) { be.err = "set_position_priors: w[" + std::to_string(k) + "] is not a finite weight >= 0"; return MVUS_E_INVALID; }
+    }
+    if (K > 0 && (be.allreduce || be.tshard.on)) {
+      be.err = "set_position_priors: position priors are not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard)";
+      return MVUS_E_UNSUPPORTED;
+    }
+    // what an LM solve left for its point -- cost, normal equations, the speculative linearisation it adopted -- belongs to the OLD set of
+    // rows: dropped, as mvus_ba_set_loss drops it (f(x) and the blocks are evaluated again, the same bits); the damping history stays
+    be.carry = LmCarry{};
+    be.set_priors(K, t, P, w);
+    if (h->schur) h->schur->carry_held();      // (blocks of the held Jacobian stay usable: the priors' pass goes on top, HipSchur::assemble_held)
+    return MVUS_OK;
+  });
+}
+
+int64_t mvus_ba_num_position_priors(const mvus_ba* h, int64_t* active_out) {
+  if (!h) return -1;
+  if (active_out) *active_out = h->be.prior_active;
+  return h->be.prior.K;
+}
+
+int mvus_ba_position_prior_cost(mvus_ba* h, const double* x, double* cost_out, double* r_out) {
+  return guarded(h, [&] {
+    HipBackend& be = h->be;
+    if (!x || !cost_out) { be.err = "position_prior_cost: NULL argument"; return MVUS_E_INVALID; }
+    if (priors_on_shards(be, "position_prior_cost")) return MVUS_E_UNSUPPORTED;
+    const int64_t K = be.prior.K;
+    *cost_out = 0.0;
+    if (K <= 0) return MVUS_OK;
+    // an inspection hook: x goes to a buffer of its own -- x_cur, the held Jacobian, f_cur and the blocks HipSchur holds stay as they are
+    PoolGuard<HipBackend> pool(be);
+    double* xd = pool.get(be.hp.n);
+    be.upload(xd, x, be.hp.n);
+    double* r = pool.get(3 * K);
+    const int pb = (int)std::min<int64_t>(2048, (K + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(k_prior_cost, dim3(pb), dim3(kThreads), 0, be.stream, be.dp, be.prior, (const double*)xd, be.partials, r);
+    hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kThreads), 0, be.stream, pb, (const double*)be.partials, be.scal_out() + 4);
+    MVUS_HIP(hipGetLastError());
+    *cost_out = 0.5 * be.read_slot(4);
+    if (h->schur) h->schur->carry_held();      // (nothing held was touched)
+    if (r_out) {
+      std::vector<double> rs((size_t)3 * K);
+      be.download(rs.data(), r, 3 * K);
+      for (int64_t k = 0; k < K; ++k)
+        for (int d = 0; d < 3; ++d) r_out[d * K + be.prior_perm[(size_t)k]] = rs[(size_t)(d * K + k)];
+    }
+    return MVUS_OK;
+  });
+}
+
 int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* weights_out) {
   return guarded(h, [&] {
     HipBackend& be = h->be;
     if (!x || !cost_out) { be.err = "robust_cost: NULL argument"; return MVUS_E_INVALID; }
     if (be.allreduce || be.tshard.on) { be.err = "robust_cost: not supported on a sharded handle"; return MVUS_E_UNSUPPORTED; }
     be.upload(be.x_cur, x, be.hp.n);
-    be.residual_sq(be.x_cur, be.f_cur, be.scal_out() + 3);      // (slot 3: outside the LM driver's, inside the host-summed range)
+    be.residual_sq(be.x_cur, be.f_cur, be.scal_out() + 3, nullptr, 0, false);      // (slot 3: outside the LM driver's, inside the host-summed range; error_BA's rows only)
     double twice = 0;
     be.fetch(be.scal_out() + 3, 1, &twice);
     *cost_out = 0.5 * twice;
@@ -1320,7 +1468,7 @@ int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
     HipBackend& be = h->be;
     if (!p_out || !(lambda >= 0)) { be.err = "lm_step: bad arguments"; return MVUS_E_INVALID; }
     if (!be.has_jacobian) { be.err = "no Jacobian held: call mvus_ba_residual_jacobian first"; return MVUS_E_INVALID; }
-    if (frozen_on_shards(be, "lm_step")) return MVUS_E_UNSUPPORTED;
+    if (frozen_on_shards(be, "lm_step") || priors_on_shards(be, "lm_step")) return MVUS_E_UNSUPPORTED;
     if (be.hp.C * (3 + be.hp.P) > 1152) throw HipError{"LM_SCHUR: reduced camera system larger than 1152 unknowns"};
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
     HipSchur<HipBackend>& sc = *h->schur;
@@ -1374,7 +1522,11 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
                                                               : nullptr;
       if (what) { be.err = std::string("a robust loss (mvus_ba_set_loss) is not supported with ") + what + ": MVUS_SOLVER_LM_SCHUR with MVUS_JAC_ANALYTIC on one rank only"; return MVUS_E_UNSUPPORTED; }
     }
-    if (frozen_on_shards(be, "solve")) return MVUS_E_UNSUPPORTED;
+    if (frozen_on_shards(be, "solve") || priors_on_shards(be, "solve")) return MVUS_E_UNSUPPORTED;
+    if (be.prior_active > 0 && opts->solver != MVUS_SOLVER_LM_SCHUR) {      // never solved with the priors silently dropped
+      be.err = "position priors (mvus_ba_set_position_priors) are not supported with MVUS_SOLVER_TRF_LSMR: MVUS_SOLVER_LM_SCHUR only";
+      return MVUS_E_UNSUPPORTED;
+    }
     SolveResult sr;
     be.held_analytic_at_xcur = false;
     if (opts->solver == MVUS_SOLVER_LM_SCHUR) {

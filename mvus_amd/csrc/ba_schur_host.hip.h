@@ -570,6 +570,9 @@ struct HipSchur {
   }
   void assemble(BE&, const double* f_dev, const double* x_fused = nullptr, const int32_t* span_held = nullptr) {
     assemble_local(f_dev, x_fused, span_held);
+    // mvus_ba_set_position_priors: the priors' rows are added behind every assembly, whatever produced the Jacobian -- at the point the fused
+    // kernel linearised, else the one the stored Jacobian was evaluated at; a handle without active priors launches nothing here
+    if (be.prior_active > 0) be.prior_normal_equations(ne, x_fused ? x_fused : be.jac_x);
     // mvus_ba_set_frozen: every assembly -- window-major, detection-major, robust, the speculative one (the bound set is the one just
     // written) -- is followed by the freeze pass; a handle without a mask launches nothing here
     if (be.frozen_count > 0) {
@@ -598,19 +601,29 @@ struct HipSchur {
   // (held_seq, carried over mvus_ba_normal_equations / lm_step / set_frozen / deterministic_fallback only -- any other entry point
   // lets it lapse), the masked system is those blocks with the freeze pass applied, entry for entry -- also behind the detection-major
   // kernel, whose atomics would give a second assembly other last bits.  A handle without a mask assembles on every call, as always.
-  uint64_t held_seq = 0;
+  // Position priors (mvus_ba_set_position_priors) the same way: blocks the call before left here WITHOUT priors receive the priors' pass on
+  // top, blocks that carry the priors in force already (held_prior_gen) are used as they are -- the difference between the exported
+  // blocks with and without priors is then the priors' contribution entry for entry on the detection-major route as well; blocks that
+  // carry OTHER priors are assembled again.  A handle with neither a mask nor active priors assembles on every call, as always.
+  uint64_t held_seq = 0, held_prior_gen = 0;
   bool held_frozen = false, held_fused = false;
   void carry_held(bool keep_frozen = true) { if (held_seq != 0 && held_seq + 1 == be.api_seq && (keep_frozen || !held_frozen)) held_seq = be.api_seq; }
   void assemble_held(BE&) {
     const bool fused = be.held_analytic_at_xcur && use_win && !sw.ne_from_j;
-    if (be.frozen_count > 0 && held_seq == be.api_seq && held_fused == fused) {
-      if (!held_frozen) {
+    const uint64_t pg = be.prior_active > 0 ? be.prior_gen : 0;
+    if ((be.frozen_count > 0 || pg != 0) && held_seq == be.api_seq && held_fused == fused && (held_prior_gen == 0 || held_prior_gen == pg) &&
+        (!held_frozen || be.frozen_count > 0)) {
+      if (held_prior_gen == 0 && pg != 0) {
+        be.prior_normal_equations(ne, fused ? be.x_cur : be.jac_x);
+        diag_pending = true;
+      }
+      if (!held_frozen && be.frozen_count > 0) {
         hipLaunchKernelGGL(k_freeze_ne, dim3((unsigned)be.frozen_count), dim3(kFreezeThreads), 0, be.stream, ne, (const int32_t*)be.frozen_idx, be.frozen_count);
         MVUS_HIP(hipGetLastError());
         diag_pending = true;
       }
     } else assemble(be, be.f_cur, fused ? be.x_cur : nullptr, fused ? be.span : nullptr);
-    held_seq = be.api_seq; held_frozen = be.frozen_count > 0; held_fused = fused;
+    held_seq = be.api_seq; held_frozen = be.frozen_count > 0; held_fused = fused; held_prior_gen = pg;
   }
 
   void flush_diag() {

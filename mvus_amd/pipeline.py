@@ -188,7 +188,8 @@ def evaluate_against_truth(flight, sc):
 def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output=True):
     """main.py:18-93 from the config.json at ``path`` (the reference's schema; ``create_scene``): every stage through
     ``StageTimer`` -- create_scene, cut_detection, init_alpha, time_shift, detection_to_global, init_traj(error=thres_Fmatix),
-    traj_to_spline, the incremental loop, spline_to_traj; ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true; ``Scene.kinematics`` (stage 'kinematics') when
+    traj_to_spline, the incremental loop, spline_to_traj; with ``settings['ba_position_priors']`` and a position log
+    (``path_position_priors``) ``Scene.align_to_position_priors`` and one final LM BA over all cameras that carries the priors; ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true; ``Scene.kinematics`` (stage 'kinematics') when
     ``settings['ba_kinematics']`` is true; ``align_gt`` when the config gives ground truth; the Scene pickled to
     ``settings['path_output']`` when ``output`` and that key is set.  Returns (Scene, StageTimer)."""
     from .reconstruction import common
@@ -201,7 +202,21 @@ def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output
     timer.run('detection_to_global', 0, flight.detection_to_global)
     timer.run('init_traj', 2, flight.init_traj, error=st.get('thres_Fmatix', 10))
     timer.run('traj_to_spline', 2, flight.traj_to_spline, smooth_factor=st['smooth_factor'])
-    incremental_reconstruction(flight, max_iter=max_iter, verbose=verbose, timer=timer)
+    priors = flight.ba_position_priors()          # (validated before the loop; None: off, or no priors given)
+    held, flight.position_priors = flight.position_priors, None      # the loop runs exactly as without them: its BAs stay gauge-free
+    try:
+        incremental_reconstruction(flight, max_iter=max_iter, verbose=verbose, timer=timer)
+    finally:
+        flight.position_priors = held
+    if priors is not None:
+        # settings['ba_position_priors']: into the surveyed frame by the similarity that fits the spline to the priors, then one LM BA over all
+        # cameras with the priors as observations; the trajectory, the covariance and the kinematics below are in that frame
+        num = flight.numCam if flight.find_order else len(flight.sequence)
+        s_, _, _, rms = timer.run('align_to_position_priors', num, flight.align_to_position_priors)
+        print('position priors: similarity of scale %.6g onto %d priors, rms %.4g' % (s_, priors[0].size, rms))
+        timer.run('BA', num, flight.BA, num, max_iter=max_iter, rs=st['rolling_shutter'], motion_reg=st['motion_reg'],
+                  motion_weights=st['motion_weights'], rs_bounds=st['rs_bounds'])
+        timer.run('spline_to_traj', num, flight.spline_to_traj, sampling_rate=1)
     flight.out = {'reconst_tran': flight.traj[1:]}
     if flight.ba_covariance_enabled():
         # settings['ba_covariance']: the covariance of the last BA's problem (all cameras of the sequence), carried by the pickle as flight.covariance

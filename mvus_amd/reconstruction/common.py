@@ -44,6 +44,13 @@ Extra ``settings`` keys (all optional; a reference ``config.json`` has none of t
                its dict (``Scene.covariance``).  DEFAULT False: nothing changes.  Needs a fixed gauge (``ba_gauge: 'anchor'`` or ``ba_freeze``).
 ``ba_kinematics`` True: ``reconstruct_from_config`` calls ``Scene.kinematics`` after ``spline_to_traj`` (after ``Scene.ba_covariance``, with its band, when
                ``ba_covariance`` is on too) and the output pickle carries its dict.  DEFAULT False: nothing changes.
+``ba_position_priors`` True with 'lm': ``Scene.position_priors`` -- surveyed positions (a GPS / RTK log) as a (7, K) array of t, x, y, z, sigma_x,
+               sigma_y, sigma_z on the spline's timeline -- enter ``Scene.BA`` as observations (``mvus_ba_set_position_priors``): three
+               non-collinear ones fix the similarity gauge, and the trajectory, the poses and their covariance come out in the surveyed
+               frame, in its unit.  ``reconstruct_from_config`` then runs its loop as always, aligns the scene to the priors
+               (``Scene.align_to_position_priors``) and ends with one LM BA over all cameras that carries them.  Not with 'trf'
+               (ValueError), and a problem the wide-band policy above would hand to TRF raises instead of dropping the priors.  DEFAULT
+               False: nothing changes.
 ``ba_deterministic`` accepted and ignored: the 'lm' solver's normal equations are assembled without floating-point atomics
                (one writer, one order of additions per entry) -- the same bits on every run by construction.
 ``opt_sync`` (reference key: False freezes alpha/beta), ``device``.
@@ -184,6 +191,7 @@ class Scene:
         self.find_order = True
         self._ba_handle = None      # GPU handle kept between BA -> remove_outliers -> BA (main.py:49-62)
         self._ba_key = None
+        self.position_priors = None    # (7, K): t, x, y, z, sigma_x, sigma_y, sigma_z of surveyed positions, or None (settings['ba_position_priors'])
 
     def __getstate__(self):         # the output pickle (main.py:93) carries data only
         state = dict(self.__dict__)
@@ -455,6 +463,8 @@ class Scene:
             mask, cur = self.ba_frozen_mask(cams), h.frozen
             if not np.array_equal(mask, cur if cur is not None else np.zeros(mask.size, dtype=bool)):
                 h.set_frozen(mask)
+        priors = self.ba_position_priors()
+        self._apply_position_priors(h, priors)
         opts = _ba._lib.default_opts(solver, jac_mode, max_iter)
         opts.lm_lambda_min = float(st.get('ba_lambda_min', opts.lm_lambda_min))
         opts.lm_trust_radius = float(st.get('ba_trust_radius', opts.lm_trust_radius))
@@ -474,6 +484,10 @@ class Scene:
                 raise _ba.UnsupportedBySolver("settings['ba_loss'] = %r needs the LM solver, which does not take this problem (%s); the fallback "
                                               "to ba_solver=trf would drop the loss -- set ba_lm_wide_band: 'lm' or ba_loss: 'linear'"
                                               % (st.get('ba_loss'), e)) from e
+            if h.num_active_position_priors:
+                # nor position priors: never solved with them dropped
+                raise _ba.UnsupportedBySolver("settings['ba_position_priors'] needs the LM solver, which does not take this problem (%s); the fallback "
+                                              "to ba_solver=trf would drop the priors -- set ba_lm_wide_band: 'lm' or ba_position_priors: false" % (e,)) from e
             # LM + Schur keeps the spline block as a band of at most sixteen 3x3 blocks (MVUS_E_UNSUPPORTED beyond; FITPACK knots far
             # below one frame apart make the motion rows reach further).  The other GPU solver has no such limit: same analytic
             # Jacobian, TRF + LSMR instead of the normal equations.  Said aloud and recorded in the result, not silently.
@@ -482,6 +496,8 @@ class Scene:
             res = h.solve(model, opts=opts, ties='canonical')
             res.solver_used = 'trf (fallback from lm: %s)' % e
         res.num_frozen = h.num_frozen
+        res.num_position_priors = h.num_position_priors
+        res.num_active_position_priors = h.num_active_position_priors
         alpha, beta, rs_new, cam_states, coefs = _problem.unpack_x(prob, res.x)
         self.alpha[cams], self.beta[cams], self.rs[cams] = alpha, beta, rs_new
         for k, i in enumerate(cams):
@@ -516,7 +532,101 @@ class Scene:
         self.ba_freeze()                     # (and ba_freeze / ba_gauge)
         self.ba_covariance_enabled()         # (and ba_covariance)
         self.ba_kinematics_enabled()         # (and ba_kinematics)
+        self.ba_position_priors()            # (and ba_position_priors / Scene.position_priors)
         return solver, modes[jac]
+
+    def ba_position_priors(self):
+        """(t (K,), P (3, K), sigma (3, K)) when settings['ba_position_priors'] is true and ``self.position_priors`` holds priors, else
+        None.  Validated on the host, before any GPU call: the flag is a bool, the array is (7, K) of finite t, x, y, z and positive
+        sigmas (inf = that axis unknown), and the solver must be 'lm'."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        v = st.get('ba_position_priors', False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("settings['ba_position_priors'] must be true or false, not %r" % (v,))
+        if not v:
+            return None
+        if st.get('ba_solver', 'trf') != 'lm':
+            raise ValueError("settings['ba_position_priors'] needs settings['ba_solver'] = 'lm' (the TRF + LSMR solver takes no position priors), "
+                             "not %r" % (st.get('ba_solver', 'trf'),))
+        pp = getattr(self, 'position_priors', None)
+        if pp is None:
+            return None
+        pp = check_position_priors(pp, 'Scene.position_priors')
+        return pp[0].copy(), pp[1:4].copy(), pp[4:7].copy()
+
+    @staticmethod
+    def _apply_position_priors(h, priors):
+        """The priors in force on the handle are ``priors`` (None: none), set only when they differ -- a handle that has them already keeps
+        what its last solve carried over, as with the loss and the mask."""
+        if priors is None:
+            if h.num_position_priors:
+                h.set_position_priors(None, None, None)
+                h._position_priors = None
+            return
+        cur = getattr(h, '_position_priors', None)
+        if cur is not None and h.num_position_priors == priors[0].size and all(np.array_equal(a, b) for a, b in zip(cur, priors)):
+            return
+        h.set_position_priors(*priors)
+        h._position_priors = priors
+
+    def _active_position_priors(self):
+        """(t, P) of the priors whose time lies in an interval of the spline (closed ends), whatever the settings say."""
+        pp = getattr(self, 'position_priors', None)
+        if pp is None:
+            return np.empty(0), np.empty((3, 0))
+        pp = check_position_priors(pp, 'Scene.position_priors')
+        iv = np.asarray(self.spline['int'], dtype=np.float64)
+        act = np.any((pp[0][None, :] >= iv[0][:, None]) & (pp[0][None, :] <= iv[1][:, None]), axis=0) if iv.size else np.zeros(pp.shape[1], bool)
+        return pp[0, act], pp[1:4, act]
+
+    def apply_similarity(self, s, R, T):
+        """Move the whole reconstruction by the similarity X -> s R X + T of the world: the control points of every spline move with it and
+        every camera keeps its image (R_c -> R_c R^T, t_c -> s t_c - R_c R^T T: the projection of the moved point is the old one, up to the
+        homogeneous factor s).  alpha, beta, rs, K and d are untouched; ``traj``, when present, moves too."""
+        s = float(s)
+        R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+        T = np.asarray(T, dtype=np.float64).reshape(3)
+        if not (np.isfinite(s) and s > 0 and np.all(np.isfinite(R)) and np.all(np.isfinite(T))):
+            raise ValueError('apply_similarity: s must be finite and positive, R and T finite')
+        for tck in self.spline['tck']:
+            c = np.asarray(tck[1], dtype=np.float64)              # [cx, cy, cz]
+            moved = s * (R @ c) + T[:, None]
+            tck[1] = [moved[0].copy(), moved[1].copy(), moved[2].copy()]
+        for c in self.cameras:
+            if getattr(c, 'R', None) is None or getattr(c, 't', None) is None:
+                continue
+            Rc = np.asarray(c.R, dtype=np.float64)
+            tc = np.ravel(np.asarray(c.t, dtype=np.float64))
+            Rn = Rc @ R.T
+            c.R, c.t = Rn, s * tc - Rn @ T
+            if c.c is not None:
+                c.c = s * (R @ np.ravel(np.asarray(c.c, dtype=np.float64))) + T
+            if c.K is not None:
+                c.compose()
+        if isinstance(self.traj, np.ndarray) and self.traj.ndim == 2 and self.traj.shape[0] == 4 and self.traj.shape[1]:
+            self.traj = np.vstack((self.traj[0], s * (R @ self.traj[1:]) + T[:, None]))
+
+    def align_to_position_priors(self):
+        """The similarity (Umeyama) that takes the spline at the active priors' times onto their positions, applied to the scene
+        (``apply_similarity``); returns (s, R, T, rms) with rms the residual of the fit.  Needs at least three active priors that are not
+        collinear -- the second singular value of the centred positions above 1e-6 of the first -- else ValueError."""
+        from scipy.interpolate import splev
+        t, P = self._active_position_priors()
+        if t.size < 3:
+            raise ValueError('align_to_position_priors: %d active position priors, at least 3 are needed' % t.size)
+        sv = np.linalg.svd(P - P.mean(axis=1, keepdims=True), compute_uv=False)
+        if not sv[1] > 1e-6 * sv[0]:
+            raise ValueError('align_to_position_priors: the active position priors are collinear (singular values %s): the similarity is not determined' % (sv,))
+        iv = np.asarray(self.spline['int'], dtype=np.float64)
+        X = np.empty((3, t.size))
+        for i in range(iv.shape[1]):
+            m = (t >= iv[0, i]) & (t <= iv[1, i])
+            if m.any():
+                X[:, m] = np.asarray(splev(t[m], self.spline['tck'][i]))
+        s, R, T = umeyama_similarity(X, P)
+        rms = float(np.sqrt(np.mean(np.sum((s * (R @ X) + T[:, None] - P) ** 2, axis=0))))
+        self.apply_similarity(s, R, T)
+        return s, R, T, rms
 
     def ba_covariance_enabled(self):
         """settings['ba_covariance'] validated (a bool; absent = False): host only."""
@@ -605,6 +715,7 @@ class Scene:
         mask, cur = self.ba_frozen_mask(cams), h.frozen
         if not np.array_equal(mask, cur if cur is not None else np.zeros(mask.size, dtype=bool)):
             h.set_frozen(mask)
+        self._apply_position_priors(h, self.ba_position_priors())
         cv = h.covariance(x, sigma2=sigma2)
         C, P = len(cams), prob.P
         names = self.ba_param_names()
@@ -902,6 +1013,54 @@ class Scene:
         return out
 
 
+def umeyama_similarity(X, Y):
+    """(s, R, T) minimising sum |s R X_i + T - Y_i|^2 over similarities (Umeyama 1991), X and Y (3, k) with k >= 3: R a proper rotation."""
+    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    mx, my = X.mean(axis=1, keepdims=True), Y.mean(axis=1, keepdims=True)
+    a, b = X - mx, Y - my
+    U, D, Vt = np.linalg.svd(b @ a.T / X.shape[1])
+    S = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2] = -1.0
+    R = U @ np.diag(S) @ Vt
+    s = float(np.sum(D * S) / (np.sum(a * a) / X.shape[1]))
+    T = (my - s * (R @ mx)).ravel()
+    return s, R, T
+
+
+def check_position_priors(pp, what='position priors'):
+    """A (7, K) float array of t, x, y, z, sigma_x, sigma_y, sigma_z, validated: finite t and positions, sigmas positive (inf allowed)."""
+    pp = np.asarray(pp, dtype=np.float64)
+    if pp.ndim != 2 or pp.shape[0] != 7:
+        raise ValueError('%s must be a (7, K) array of t, x, y, z, sigma_x, sigma_y, sigma_z, not shape %s' % (what, pp.shape))
+    if not np.all(np.isfinite(pp[:4])):
+        raise ValueError('%s: a time or a position is not finite' % what)
+    if np.any(np.isnan(pp[4:])) or np.any(pp[4:] <= 0):
+        raise ValueError('%s: sigma must be positive (inf leaves an axis out)' % what)
+    return pp
+
+
+def load_position_priors(path, default_sigma=None):
+    """A text file with the columns t x y z [sigma_x sigma_y sigma_z] (one prior per line, ``#`` comments) -> (7, K).  Files without the sigma
+    columns take ``default_sigma`` (a positive number, or three of them)."""
+    try:
+        a = np.loadtxt(path, dtype=np.float64, ndmin=2)
+    except ValueError as e:
+        raise ValueError('position priors %s: %s' % (path, e)) from None
+    if a.shape[0] == 0:
+        return np.empty((7, 0))
+    if a.shape[1] == 4:
+        if default_sigma is None:
+            raise ValueError("position priors %s: columns t x y z only -- give sigma_x sigma_y sigma_z columns or 'position_prior_sigma'" % path)
+        sg = np.asarray(default_sigma, dtype=np.float64)
+        if sg.shape not in ((), (3,)) or isinstance(default_sigma, bool):
+            raise ValueError("'position_prior_sigma' must be a positive number or three of them, not %r" % (default_sigma,))
+        a = np.hstack((a, np.broadcast_to(sg, (a.shape[0], 3))))
+    elif a.shape[1] != 7:
+        raise ValueError('position priors %s: %d columns, expected t x y z [sigma_x sigma_y sigma_z]' % (path, a.shape[1]))
+    return check_position_priors(a.T.copy(), 'position priors %s' % path)
+
+
 def create_scene(path_input):
     """Build a Scene from the reference's JSON config (common.py:1171-1230): sections
     'necessary inputs', 'optional inputs', 'settings'."""
@@ -937,5 +1096,10 @@ def create_scene(path_input):
         flight.rs = np.full(flight.numCam, float(init_rs))
     if 'optional inputs' in config and 'ground_truth' in config['optional inputs']:
         flight.gt = config['optional inputs']['ground_truth']
+    opt = config.get('optional inputs', {})
+    if opt.get('path_position_priors'):
+        # surveyed positions (GPS / RTK log): t x y z [sigma_x sigma_y sigma_z] per line, t on the reference camera's frame clock
+        flight.position_priors = load_position_priors(opt['path_position_priors'], opt.get('position_prior_sigma'))
+    flight.ba_position_priors()              # (settings['ba_position_priors'] validated here, before any GPU work)
     print('Input data are loaded successfully, a scene is created.\n')
     return flight
