@@ -243,6 +243,21 @@ int mvus_ba_normal_equations(mvus_ba* h, double* g, double* JtJ_cam, double* ban
  * (assembly, band solver, Schur complement, reduced system); no trial evaluation, no bounds.  No reference counterpart. */
 int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out);
 
+/* The linear solve of MVUS_SOLVER_TRF_LSMR on its own: LSMR (Fong & Saunders, scipy.sparse.linalg.lsmr) on
+ *   A = [J diag(D); diag(E)],  right-hand side [b; 0],  min |A x - [b; 0]|^2 + damp^2 |x|^2,  x started from 0,
+ * with the Jacobian currently held (after mvus_ba_residual_jacobian).  b[m]; D[n], E[n] or NULL (D = 1, no extra rows): the column scaling
+ * and the extra diagonal rows of scipy's trf_bounds; atol, btol, conlim as scipy's (0: that test never stops the run); maxiter <= 0:
+ * min(rows of A, n).  Inspection hook for the solver's loop -- the device-resident iteration, and whatever MVUS_LSMR_HOST,
+ * MVUS_LSMR_BOUNDED_HOST (read when the handle was created) and MVUS_LSMR_ONE_PASS (read at every run) select.  With a frozen mask in
+ * force the frozen columns of J are zero, as inside a solve, and x[k] = 0.0 there.  No reference counterpart.
+ *   x_out[n];  *itn_out iterations run;  *istop_out scipy's istop (7: maxiter);  norms_out[4] = normr, normar, normA, condA at return
+ *   (itn_out, istop_out, norms_out may be NULL).
+ * Changes no state of the handle: the held Jacobian, residual and point, the damping history and what a later mvus_ba_solve returns stay.
+ * MVUS_E_INVALID: b or x_out NULL, damp < 0 or NaN, no Jacobian held.  MVUS_E_UNSUPPORTED: a sharded handle (set_allreduce / set_rccl /
+ * set_time_shard). */
+int mvus_ba_lsmr(mvus_ba* h, const double* b, const double* D, const double* E, double damp, double atol, double btol, double conlim,
+                 int64_t maxiter, double* x_out, int32_t* itn_out, int32_t* istop_out, double* norms_out);
+
 /* Robust loss: least_squares(..., loss=, f_scale=) of common.py:670 (the reference passes neither: linear, 1.0).  With z = (f_i / f_scale)^2
  * for EVERY row of f (motion rows included, as scipy does with error_BA):
  *   MVUS_LOSS_LINEAR rho = z | SOFT_L1 2 (sqrt(1 + z) - 1) | HUBER z if z <= 1 else 2 sqrt(z) - 1 | CAUCHY log(1 + z) | ARCTAN atan(z)

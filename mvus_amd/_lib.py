@@ -83,6 +83,8 @@ API = [
     ('mvus_ba_jtu', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p]),
     ('mvus_ba_normal_equations', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
     ('mvus_ba_lm_step', ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p]),
+    ('mvus_ba_lsmr', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_int64, c_double_p, c_int32_p, c_int32_p, c_double_p]),
     ('mvus_ba_set_loss', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
     ('mvus_ba_set_frozen', ctypes.c_int, [ctypes.c_void_p, c_uint8_p, ctypes.c_int64]),
     ('mvus_ba_num_frozen', ctypes.c_int64, [ctypes.c_void_p]),

@@ -245,6 +245,21 @@ class BAHandle:
         self._check(self.lib.mvus_ba_lm_step(self.h, float(lam), _lib.dptr(p)), 'mvus_ba_lm_step')
         return p
 
+    def lsmr(self, b, D=None, E=None, damp=0.0, atol=1e-6, btol=1e-6, conlim=1e8, maxiter=0):
+        """LSMR on A = [J diag(D); diag(E)] with right-hand side [b; 0] for the Jacobian currently held (after residual_jacobian): the linear
+        solve of the TRF + LSMR solver on its own (mvus_ba_lsmr), by the loop the handle's switches select.  Returns a namespace
+        (x, itn, istop, normr, normar, normA, condA).  Changes nothing a later solve sees."""
+        b = self._x(b, self.m)
+        D = self._x(D, self.n) if D is not None else None
+        E = self._x(E, self.n) if E is not None else None
+        x = np.empty(self.n)
+        itn, istop = ctypes.c_int32(0), ctypes.c_int32(0)
+        norms = np.zeros(4)
+        self._check(self.lib.mvus_ba_lsmr(self.h, _lib.dptr(b), _lib.dptr(D) if D is not None else None, _lib.dptr(E) if E is not None else None,
+                                          float(damp), float(atol), float(btol), float(conlim), int(maxiter), _lib.dptr(x),
+                                          ctypes.byref(itn), ctypes.byref(istop), _lib.dptr(norms)), 'mvus_ba_lsmr')
+        return SimpleNamespace(x=x, itn=itn.value, istop=istop.value, normr=norms[0], normar=norms[1], normA=norms[2], condA=norms[3])
+
     def set_loss(self, loss, f_scale=1.0):
         """least_squares(loss=, f_scale=): the robust loss of every later solve / normal_equations / lm_step on the handle (LM + Schur,
         analytic Jacobian, one rank).  residual, residual_jacobian, jv, jtu and the outlier masks stay those of error_BA."""

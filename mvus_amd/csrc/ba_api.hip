@@ -1482,6 +1482,51 @@ int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
   });
 }
 
+int mvus_ba_lsmr(mvus_ba* h, const double* b, const double* D, const double* E, double damp, double atol, double btol, double conlim,
+                 int64_t maxiter, double* x_out, int32_t* itn_out, int32_t* istop_out, double* norms_out) {
+  return guarded(h, [&] {
+    HipBackend& be = h->be;
+    if (!b || !x_out || !(damp >= 0)) { be.err = "lsmr: bad arguments"; return MVUS_E_INVALID; }
+    if (be.allreduce || be.tshard.on) { be.err = "lsmr: not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
+    if (!be.has_jacobian) { be.err = "no Jacobian held: call mvus_ba_residual_jacobian first"; return MVUS_E_INVALID; }
+    // an inspection hook: b, D, E and x live in buffers of their own -- x_cur, f_cur, the held Jacobian and the blocks HipSchur holds stay
+    // as they are.  With a mask in force the solver's Jacobian is the frozen one (k_freeze_jacobian, as inside a TRF solve): the held
+    // blocks are set aside and put back, so mvus_ba_jv / jtu / lm_step after the call still see error_BA's own
+    const int64_t n = be.hp.n, m = be.hp.m;
+    PoolGuard<HipBackend> pool(be);
+    double* bd = pool.get(m);
+    double* xd = pool.get(n);
+    double* Dd = D ? pool.get(n) : nullptr;
+    double* Ed = E ? pool.get(n) : nullptr;
+    be.upload(bd, b, m);
+    if (D) be.upload(Dd, D, n);
+    if (E) be.upload(Ed, E, n);
+    const int64_t jlen = (int64_t)j_doubles(be.hp.NS, be.dp.n_chunks);
+    double* Jsave = nullptr;
+    if (be.frozen_count > 0 && be.dp.n_chunks > 0) {
+      Jsave = pool.get(jlen);
+      MVUS_HIP(hipMemcpyAsync(Jsave, be.J, sizeof(double) * jlen, hipMemcpyDeviceToDevice, be.stream));
+      be.freeze_jacobian();
+    }
+    struct Restore {      // (also when the run throws)
+      HipBackend& be; double* save; int64_t len;
+      ~Restore() { if (save) { (void)hipMemcpyAsync(be.J, save, sizeof(double) * len, hipMemcpyDeviceToDevice, be.stream); (void)hipStreamSynchronize(be.stream); } }
+    } restore{be, Jsave, jlen};
+    LsmrScalars sc;
+    int itn = 0, istop = 0;
+    {
+      Lsmr<HipBackend> lsmr(be);
+      istop = lsmr.run(Dd, Ed, bd, damp, atol, btol, conlim, maxiter > 0 ? maxiter : std::min<int64_t>(m + (E ? n : 0), n), xd, &itn, &sc);
+    }
+    be.download(x_out, xd, n);
+    if (itn_out) *itn_out = itn;
+    if (istop_out) *istop_out = istop;
+    if (norms_out) { norms_out[0] = sc.normr; norms_out[1] = sc.normar; norms_out[2] = sc.normA; norms_out[3] = sc.condA; }
+    if (h->schur) h->schur->carry_held();      // (nothing held was touched)
+    return MVUS_OK;
+  });
+}
+
 int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_result* res, double* f_out) {
   return guarded(h, [&] {
     HipBackend& be = h->be;

@@ -398,7 +398,7 @@ struct Lsmr {
   }
 
   int run(const double* D, const double* E, const double* b_top, double damp, double atol, double btol, double conlim,
-          int64_t maxiter, double* x, int* itn_out) {
+          int64_t maxiter, double* x, int* itn_out, LsmrScalars* sc_out = nullptr) {
     using detail::sym_ortho;
     const bool trace = lsmr_trace_now();
     be.copy(ut, b_top, m);
@@ -422,6 +422,7 @@ struct Lsmr {
     sc.ctol = conlim > 0 ? 1 / conlim : 0;
     sc.normr = beta; sc.normar = alpha * beta; sc.normA = std::sqrt(sc.normA2); sc.maxiter = maxiter;
     if (itn_out) *itn_out = 0;
+    if (sc_out) *sc_out = sc;      // (the scalars at return: normr, normar, normA, condA, itn, istop -- mvus_ba_lsmr)
     if (sc.normar == 0) return 0;
     if (normb == 0) { be.fill(x, 0.0, n); return 0; }
     if constexpr (B::kDeviceLsmr) {
@@ -430,6 +431,7 @@ struct Lsmr {
       if (!trace && be.lsmr_on_device() && (!(D || E) || be.lsmr_scaled_on_device())) {
         be.lsmr_iterations(sc, ut, tm, v, tn, h, hbar, x, D, E, ub);
         if (itn_out) *itn_out = (int)sc.itn;
+        if (sc_out) *sc_out = sc;
         return sc.istop;
       }
     }
@@ -469,6 +471,7 @@ struct Lsmr {
     const int64_t itn = sc.itn;
     const int istop = sc.istop;
     if (itn_out) *itn_out = (int)itn;
+    if (sc_out) *sc_out = sc;
     return istop;
   }
 };

@@ -23,13 +23,14 @@ struct Switches {
   bool no_spec_shards = false;
   // MVUS_SQ_DEVICE_SUM (set): |f|^2 finished by k_dot_final instead of the host-side sum of the partials.  Default off.  test_gpu_schur.py.
   bool sq_device_sum = false;
-  // MVUS_LSMR_HOST (set): the host-driven LSMR loop instead of the device-resident one.  Default off.  A/B by hand.
+  // MVUS_LSMR_HOST (set): the host-driven LSMR loop instead of the device-resident one.  Default off.  test_gpu_lsmr.py (the two loops
+  // bit for bit, through mvus_ba_lsmr).
   bool lsmr_host = false;
-  // MVUS_LSMR_BOUNDED_HOST (set): the bounded problem's LSMR on the host-driven loop.  Default off.  test_gpu_parity.py.
+  // MVUS_LSMR_BOUNDED_HOST (set): the bounded problem's LSMR on the host-driven loop.  Default off.  test_gpu_parity.py, test_gpu_lsmr.py.
   bool lsmr_bounded_host = false;
   // MVUS_LSMR_ONE_PASS (set): one pass over J per LSMR iteration (k_jvjtu).  Default off.  PER RUN: bench.py sets and clears it on a
   // live handle, so the backend asks lsmr_one_pass_now() at every LSMR run; this field is the value when the table was read.
-  // test_gpu_parity.py, bench.py.
+  // test_gpu_lsmr.py (against a longdouble LSMR at every branch of k_jvjtu), test_gpu_parity.py, bench.py.
   bool lsmr_one_pass = false;
   // MVUS_LSMR_TRACE (set): Lsmr::run prints its scalars every iteration.  Default off.  PER RUN (lsmr_trace_now(): ba_solver.h has no
   // handle to keep a table on).  Debugging by hand.

@@ -413,12 +413,43 @@ int hostcheck_solve(void* h, double* x, const mvus_solve_opts* o, mvus_result* r
 
 }  // extern "C"
 
-// LSMR on the Jacobian currently held (after hostcheck_dense_jacobian): min |J x - b|^2 + damp^2 |x|^2
-extern "C" int hostcheck_lsmr(void* h, const double* b, double damp, double atol, double btol, double conlim,
-                              int maxiter, double* x_out, int* itn) {
+// first control point of every detection row of the Jacobian currently held (-1: not visible), what mvus_ba_residual_jacobian returns as ctrl
+extern "C" int hostcheck_spans(void* h, int32_t* ctrl) {
   HostBackend* be = static_cast<HostBackend*>(h);
-  Lsmr<HostBackend> l(*be);
-  return l.run(nullptr, nullptr, b, damp, atol, btol, conlim, maxiter > 0 ? maxiter : std::min(be->hp.m, be->hp.n), x_out, itn);
+  if (be->hp.M > 0) std::memcpy(ctrl, be->span.data(), sizeof(int32_t) * be->hp.M);
+  return 0;
+}
+
+// LSMR on the Jacobian currently held (after hostcheck_dense_jacobian), the host build of mvus_ba_lsmr: A = [J diag(D); diag(E)] (D, E
+// n-vectors or NULL), right-hand side [b; 0], damping `damp`.  frozen: NULL or a mask over the head of x in pack_x order (C * (3 + P)
+// entries, as mvus_ba_set_frozen takes it) -- those columns of the stored J are zero during the run, as k_freeze_jacobian leaves them, and
+// put back after it.  norms_out[4] = normr, normar, normA, condA at return.
+extern "C" int hostcheck_lsmr(void* h, const double* b, const double* D, const double* E, const uint8_t* frozen, double damp, double atol,
+                              double btol, double conlim, int64_t maxiter, double* x_out, int32_t* itn_out, int32_t* istop_out, double* norms_out) {
+  HostBackend* be = static_cast<HostBackend*>(h);
+  const int64_t n = be->hp.n, m = be->hp.m, M = be->hp.M;
+  const int C = be->hp.C, P = be->hp.P, NS = be->hp.NS;
+  std::vector<double> saved;
+  if (frozen) {
+    saved = be->J;
+    for (int64_t k = 0; k < (int64_t)C * (3 + P); ++k) {
+      if (!frozen[k]) continue;
+      const int c = k < 3 * C ? (int)(k % C) : (int)((k - 3 * C) / P);
+      const int slot = k < 3 * C ? (int)(k / C) : 3 + (int)((k - 3 * C) % P);
+      for (int64_t i = be->hp.det_off[c]; i < be->hp.det_off[c + 1]; ++i) { be->J[(size_t)slot * M + i] = 0.0; be->J[(size_t)(NS + slot) * M + i] = 0.0; }
+    }
+  }
+  LsmrScalars sc;
+  int itn = 0, istop = 0;
+  {
+    Lsmr<HostBackend> l(*be);
+    istop = l.run(D, E, b, damp, atol, btol, conlim, maxiter > 0 ? maxiter : std::min<int64_t>(m + (E ? n : 0), n), x_out, &itn, &sc);
+  }
+  if (frozen) be->J = saved;
+  if (itn_out) *itn_out = itn;
+  if (istop_out) *istop_out = istop;
+  if (norms_out) { norms_out[0] = sc.normr; norms_out[1] = sc.normar; norms_out[2] = sc.normA; norms_out[3] = sc.condA; }
+  return 0;
 }
 
 // partition of a control-point chain (ba_partition.h): returns the number of interiors, fills i0/i1 (scalar rows) and the

@@ -41,6 +41,9 @@ def load():
     lib.hostcheck_upload_pattern.argtypes = [ctypes.c_void_p, _lib.c_int32_p, _lib.c_int32_p]
     lib.hostcheck_set_fd_groups.argtypes = [ctypes.c_void_p, _lib.c_int32_p, ctypes.c_int]
     lib.hostcheck_jtu.argtypes = [ctypes.c_void_p, _lib.c_double_p, _lib.c_double_p]
+    lib.hostcheck_spans.argtypes = [ctypes.c_void_p, _lib.c_int32_p]
+    lib.hostcheck_lsmr.argtypes = [ctypes.c_void_p, _lib.c_double_p, _lib.c_double_p, _lib.c_double_p, _lib.c_uint8_p] + [ctypes.c_double] * 4 \
+        + [ctypes.c_int64, _lib.c_double_p, _lib.c_int32_p, _lib.c_int32_p, _lib.c_double_p]
     lib.hostcheck_solve.argtypes = [ctypes.c_void_p, _lib.c_double_p, ctypes.POINTER(_lib.MvusSolveOpts),
                                     ctypes.POINTER(_lib.MvusResult), _lib.c_double_p]
     lib.hostcheck_triangulate.argtypes = [ctypes.c_longlong] + [_lib.c_double_p] * 7
@@ -145,6 +148,29 @@ class HostHandle:
         z = np.zeros(self.n)
         self.lib.hostcheck_jtu(self.h, _lib.dptr(u), _lib.dptr(z))
         return z
+
+    def spans(self):
+        """ctrl[M] of the Jacobian the last dense_jacobian left: the first control point of every detection (-1: not visible)."""
+        ctrl = np.zeros(self.prob.M, dtype=np.int32)
+        self.lib.hostcheck_spans(self.h, ctrl.ctypes.data_as(_lib.c_int32_p))
+        return ctrl
+
+    def lsmr(self, b, D=None, E=None, damp=0.0, atol=1e-6, btol=1e-6, conlim=1e8, maxiter=0, frozen=None):
+        """BAHandle.lsmr over the plain C++ backend, on the Jacobian the last dense_jacobian left (``frozen``: the mask set_frozen takes)."""
+        from types import SimpleNamespace
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        assert b.shape == (self.m,)
+        D = np.ascontiguousarray(D, dtype=np.float64) if D is not None else None
+        E = np.ascontiguousarray(E, dtype=np.float64) if E is not None else None
+        fz = np.ascontiguousarray(frozen, dtype=np.uint8).reshape(-1) if frozen is not None else None
+        assert fz is None or fz.size == self.prob.C * (3 + self.prob.P)
+        x = np.zeros(self.n)
+        itn, istop = ctypes.c_int32(0), ctypes.c_int32(0)
+        norms = np.zeros(4)
+        self.lib.hostcheck_lsmr(self.h, _lib.dptr(b), _lib.dptr(D) if D is not None else None, _lib.dptr(E) if E is not None else None,
+                                fz.ctypes.data_as(_lib.c_uint8_p) if fz is not None else None, float(damp), float(atol), float(btol),
+                                float(conlim), int(maxiter), _lib.dptr(x), ctypes.byref(itn), ctypes.byref(istop), _lib.dptr(norms))
+        return SimpleNamespace(x=x, itn=itn.value, istop=istop.value, normr=norms[0], normar=norms[1], normA=norms[2], condA=norms[3])
 
     def solve(self, x0, opts, ties='numpy', matrix=None):
         x = np.array(x0, dtype=np.float64)
