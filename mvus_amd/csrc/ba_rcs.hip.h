@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void k_rcs_finish(NEView ne, int ncols, int ns
 #pragma unroll
   for (int q = 0; q < kRowsPer; ++q) {
     const int a = blockIdx.y * kT + r0 + kRowStep * q;
-    const int hi = a / kGemmT >= b / kGemmT ? a : b, lo = a / kGemmT >= b / kGemmT ? b : a;
+    const int hi = a / 16 >= b / 16 ? a : b, lo = a / 16 >= b / 16 ? b : a;      // (k_schur_gemm computes the 16x16 sub-blocks on or below the diagonal)
     goff[q] = (a < nn && b < nn) ? (long long)hi * ncols + lo : -1;
     gsum[q] = 0.0;
   }

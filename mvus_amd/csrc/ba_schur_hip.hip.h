@@ -28,6 +28,7 @@
 
 #include "ba_kernels.hip.h"
 #include "ba_partition.h"
+#include "ba_gemm_plan.h"
 #include "ba_schur.h"
 
 namespace mvus {
@@ -2038,35 +2039,37 @@ __global__ __launch_bounds__(256) void k_cholesky_and_rhs(PartView pv, double* _
 // contiguous bytes), so fragments go from global memory straight to registers -- no LDS staging.  One wavefront owns a
 // 48x48 output tile (3x3 MFMA tiles, 36 accumulator registers) over wave_k rows of K; the four wavefronts of a
 // workgroup take consecutive K ranges of the same tile and are summed through LDS.  Et^T C^-1 Et is symmetric: only
-// tiles on or below the block diagonal are computed (k_schur_finish mirrors), plus one 48x16 tile per block row for
-// the right-hand-side column.  Partial sums per slab are written, not atomically added: no memset, deterministic.
+// 16x16 sub-blocks on or below the diagonal are computed (k_schur_finish and k_rcs_finish mirror).  In a tile ON the block
+// diagonal that leaves three of the nine accumulators free -- (0,1), (0,2), (1,2) --, and they take the right-hand-side
+// column: a fourth B fragment, column CB of the second operand, against the tile's three A fragments (ba_gemm_plan.h:
+// gemm_sub).  So the column costs no tile, no matrix-core instruction and no read of an A strip of its own: nbk (nbk + 1) / 2
+// tiles, nine useful sub-blocks each (it does cost the diagonal tiles a seventh fragment load per k-step: DESIGN 4.5).  Partial sums per slab are written, not atomically added: no memset, deterministic;
+// the three sub-blocks above the diagonal of a diagonal tile are never written and never read.
 using d4 = __attribute__((ext_vector_type(4))) double;
-constexpr int kGemmT = 48;
-constexpr int kGemmUn = 4;                                 // k-steps (of 4 rows) per operand set
-constexpr int kGemmSetRows = 4 * kGemmUn;
 
-// Operand sets of the Schur product: kGemmUn k-steps of a 48-wide A strip and a 16 NJ-wide B strip, one double per lane and
+// Operand sets of the Schur product: kGemmUn k-steps of a 48-wide A strip and NB B fragments of 16 columns (NB = 3: a 48-wide B
+// strip; NB = 4, the diagonal tiles: + the rhs column), one double per lane and
 // 16 x 4 fragment.  Two sets are alive: the loads of set k+1 are issued before the matrix-core instructions of set k
 // (a lone wavefront per SIMD otherwise waits out the full memory latency once per set: 58 us instead of 27 at configs[2]).
-template <int NJ>
+template <int NB>
 struct GemmSet {
-  double a[kGemmUn][3], b[kGemmUn][NJ];
+  double a[kGemmUn][3], b[kGemmUn][NB];
   // ap / bp point at this lane's row (k + lane / 16) and first column; every address is inside the arrays (columns beyond the
   // matrix are clamped by the caller: they only feed output rows / columns that are never stored), so the loads carry no
   // predicate and no branch -- the steady-state loop below is one basic block and s_waitcnt can count the younger set's loads.
   __device__ __forceinline__ void load(const double* __restrict__ ap, const double* __restrict__ bp, long long lda, long long ldb,
-                                       const int (&ao)[3], const int (&bo)[NJ]) {
+                                       const int (&ao)[3], const int (&bo)[NB]) {
 #pragma unroll
     for (int u = 0; u < kGemmUn; ++u) {
 #pragma unroll
       for (int i = 0; i < 3; ++i) a[u][i] = ap[(long long)(4 * u) * lda + ao[i]];
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) b[u][j] = bp[(long long)(4 * u) * ldb + bo[j]];
+      for (int j = 0; j < NB; ++j) b[u][j] = bp[(long long)(4 * u) * ldb + bo[j]];
     }
   }
   // the last, possibly partial set of the whole product: rows clamped to the last one, their values replaced by zero
   __device__ __forceinline__ void load_tail(const double* __restrict__ A, const double* __restrict__ B, long long lda, long long ldb,
-                                            const int (&ao)[3], const int (&bo)[NJ], int k, int k1, int lk) {
+                                            const int (&ao)[3], const int (&bo)[NB], int k, int k1, int lk) {
 #pragma unroll
     for (int u = 0; u < kGemmUn; ++u) {
       const int row = k + 4 * u + lk;
@@ -2075,24 +2078,29 @@ struct GemmSet {
 #pragma unroll
       for (int i = 0; i < 3; ++i) { const double v = A[rc * lda + ao[i]]; a[u][i] = kv ? v : 0.0; }
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) { const double v = B[rc * ldb + bo[j]]; b[u][j] = kv ? v : 0.0; }
+      for (int j = 0; j < NB; ++j) { const double v = B[rc * ldb + bo[j]]; b[u][j] = kv ? v : 0.0; }
     }
   }
-  __device__ __forceinline__ void multiply(d4 (&acc)[3][NJ]) const {
+  // NB = 3: all nine sub-blocks.  NB = 4: the six with j <= i, and a0, a1, a2 against the rhs fragment into (0,1), (0,2), (1,2)
+  __device__ __forceinline__ void multiply(d4 (&acc)[3][3]) const {
 #pragma unroll
     for (int u = 0; u < kGemmUn; ++u)
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][i], b[u][j], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < 3; ++j) {
+          const GemmSub sb = gemm_sub(NB == 4, i, j);          // (folds: i, j are unrolled)
+          if (sb.rhs) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][sb.rb], b[u][NB - 1], acc[i][j], 0, 0, 0);
+          else acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][i], b[u][j], acc[i][j], 0, 0, 0);
+        }
   }
 };
 
 // sets [s_lo, s_hi) of 16 rows of ONE operand pair (A row stride lda with per-lane offsets ao, B row stride ldb with bo), rows
 // [row_lo, row_hi): only the pair's very last set can be partial
-template <int NJ>
-__device__ __forceinline__ void schur_gemm_sets(d4 (&acc)[3][NJ], const double* __restrict__ A, const double* __restrict__ Bm, long long lda, long long ldb,
-                                                const int (&ao)[3], const int (&bo)[NJ], int row_lo, int row_hi, int s_lo, int s_hi, int lk) {
+template <int NB>
+__device__ __forceinline__ void schur_gemm_sets(d4 (&acc)[3][3], const double* __restrict__ A, const double* __restrict__ Bm, long long lda, long long ldb,
+                                                const int (&ao)[3], const int (&bo)[NB], int row_lo, int row_hi, int s_lo, int s_hi, int lk) {
   if (s_hi <= s_lo) return;
   const int nsets = (row_hi - row_lo + kGemmSetRows - 1) / kGemmSetRows;
   const bool tail = s_hi == nsets && (row_hi - row_lo) % kGemmSetRows != 0;
@@ -2101,7 +2109,7 @@ __device__ __forceinline__ void schur_gemm_sets(d4 (&acc)[3][NJ], const double* 
   const double* ap = A + (long long)(k0 + lk) * lda;
   const double* bp = Bm + (long long)(k0 + lk) * ldb;
   const long long sa = kGemmSetRows * lda, sb = kGemmSetRows * ldb;
-  GemmSet<NJ> s0, s1;
+  GemmSet<NB> s0, s1;
   if (nfull > 0) {
     s0.load(ap, bp, lda, ldb, ao, bo);
     int si = 0;
@@ -2128,18 +2136,18 @@ __device__ __forceinline__ void schur_gemm_sets(d4 (&acc)[3][NJ], const double* 
 // The product's K range is the rows [row_lo, row_hi) of (Ecm, Z) followed by the rows [0, sep_rows) of the compact pair (Dl, Xs) -- the
 // separators' correction term (one rank, round 5; sep_rows = 0: none) --, cut into sets of 16; wavefront g of nslab * 4 takes sets
 // [g q + min(g, r), ...) with q, r = nsets / nwaves, nsets % nwaves of the WHOLE range: every wavefront within one set of the others.
-template <int NJ>   // NJ = 3: 48x48 tile of the symmetric part, NJ = 1: 48x16 tile holding the rhs column
+template <int NB>   // NB = 3: 48x48 tile below the block diagonal; NB = 4: tile on it, lower triangle + the rhs column (a0 == b0)
 __device__ __forceinline__ void schur_gemm_tile(const NEView& ne, int ncols, const double* __restrict__ Ecm, const double* __restrict__ Z,
                                                 double* __restrict__ Gp, int a0, int b0, int row_lo, int row_hi, int slab, int nslab, double* red,
                                                 const double* __restrict__ Dl, const double* __restrict__ Xs, int sep_rows) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  d4 acc[3][NJ];
+  d4 acc[3][3];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-  int ao[3], ac[3], bo[NJ];
+    for (int j = 0; j < 3; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+  int ao[3], ac[3], bo[NB];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {                                // A = the cross block where the assembly left it (camera-major [C][3N][B]):
     const int col = min(a0 + 16 * i + lr, ne.CB - 1);          // column (c, k) of row r is Et[(c N3 + r) B + k] -- row stride B, per-lane offset
@@ -2147,32 +2155,39 @@ __device__ __forceinline__ void schur_gemm_tile(const NEView& ne, int ncols, con
     ac[i] = col;                                               // (the compact pair is row-major [rows][CB])
   }
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) bo[j] = NJ == 3 ? min(b0 + 16 * j + lr, ne.CB - 1) : ne.CB;
+  for (int j = 0; j < NB; ++j) bo[j] = j < 3 ? min(b0 + 16 * j + lr, ne.CB - 1) : ne.CB;      // (the rhs fragment: column CB of Z and of Xs in every lane)
   const int nmain = (row_hi - row_lo + kGemmSetRows - 1) / kGemmSetRows, ncorr = (sep_rows + kGemmSetRows - 1) / kGemmSetRows;
   const int nsets = nmain + ncorr, nwaves = nslab * 4, g = slab * 4 + wave;
   const int q = nsets / nwaves, r = nsets % nwaves;
   const int s_lo = g * q + min(g, r), s_hi = s_lo + q + (g < r ? 1 : 0);
-  schur_gemm_sets<NJ>(acc, Ecm, Z, ne.B, ncols, ao, bo, row_lo, row_hi, min(s_lo, nmain), min(s_hi, nmain), lk);
-  if (ncorr > 0) schur_gemm_sets<NJ>(acc, Dl, Xs, ne.CB, ncols, ac, bo, 0, sep_rows, max(s_lo, nmain) - nmain, max(s_hi, nmain) - nmain, lk);
-  // sum the four wavefronts through LDS, then store: element (i, j, reg) of lane l is row 16i + (l>>4) + 4 reg, col 16j + (l&15)
+  schur_gemm_sets<NB>(acc, Ecm, Z, ne.B, ncols, ao, bo, row_lo, row_hi, min(s_lo, nmain), min(s_hi, nmain), lk);
+  if (ncorr > 0) schur_gemm_sets<NB>(acc, Dl, Xs, ne.CB, ncols, ac, bo, 0, sep_rows, max(s_lo, nmain) - nmain, max(s_hi, nmain) - nmain, lk);
+  // sum the four wavefronts through LDS, then store: element (reg) of lane l of a 16x16 sub-block is its row (l>>4) + 4 reg, column l&15
   for (int w = 0; w < 4; ++w) {
     if (wave == w) {
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
+        for (int j = 0; j < 3; ++j)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            double* dst = red + ((i * NJ + j) * 4 + r) * 64 + lane;
+            double* dst = red + ((i * 3 + j) * 4 + r) * 64 + lane;
             *dst = (w == 0 ? 0.0 : *dst) + acc[i][j][r];
           }
     }
     __syncthreads();
   }
-  for (int e = threadIdx.x; e < 3 * NJ * 4 * 64; e += 256) {
-    const int l = e & 63, r = (e >> 6) & 3, ij = e >> 8, i = ij / NJ, j = ij % NJ;
-    const int row = a0 + 16 * i + (l >> 4) + 4 * r, col = b0 + 16 * j + (l & 15);
-    if (row < ne.CB && col < ncols && (NJ == 3 ? col < ne.CB : (l & 15) == 0)) Gp[(long long)row * ncols + col] = red[e];
+  for (int e = threadIdx.x; e < 9 * 4 * 64; e += 256) {
+    const int l = e & 63, r = (e >> 6) & 3, ij = e >> 8;
+    const GemmSub sb = gemm_sub(NB == 4, ij / 3, ij % 3);
+    const int row = a0 + 16 * sb.rb + (l >> 4) + 4 * r;
+    if (row >= ne.CB) continue;
+    if (sb.rhs) {                                            // sixteen equal columns: the first one is G[row][CB]
+      if ((l & 15) == 0) Gp[(long long)row * ncols + ne.CB] = red[e];
+    } else {
+      const int col = b0 + 16 * sb.cb + (l & 15);
+      if (col < ne.CB) Gp[(long long)row * ncols + col] = red[e];
+    }
   }
 }
 
@@ -2180,27 +2195,22 @@ __device__ __forceinline__ void schur_gemm_tile(const NEView& ne, int ncols, con
 // strip: all workgroups of a slab go to ONE XCD (workgroup L runs on XCD L % 8: slab = L % 8 + 8 * (L / 8 / tiles)), so a strip
 // comes from HBM once and from that XCD's L2 afterwards (with the slabs dealt over all XCDs every XCD fetched every strip:
 // 154 - 308 MB for 55 MB of operands, and the kernel ran at the fabric's rate, not the matrix cores').  Grid: 8 * tiles *
-// ceil(nslab / 8) workgroups; the slab count is chosen by the host (HipSchur::plan_gemm) to fill whole rounds of the XCD's slots.
+// ceil(nslab / 8) workgroups (gemm_grid); the slab count is chosen by the host (gemm_plan_slabs) to fill whole rounds of the XCD's slots.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_schur_gemm(NEView ne, int ncols, int row_lo, int row_hi, int nslab, const double* __restrict__ Ecm, const double* __restrict__ Z, double* __restrict__ Gp,
                   const double* __restrict__ Dl = nullptr, const double* __restrict__ Xs = nullptr, int sep_rows = 0) {
   __shared__ double red[9 * 4 * 64];
-  const int nbk = (ne.CB + kGemmT - 1) / kGemmT, nsym = nbk * (nbk + 1) / 2, tiles = nsym + nbk;
+  const int tiles = gemm_tiles(ne.CB);
   const int L = blockIdx.x, j = L >> 3;
   const int slab = (L & 7) + 8 * (j / tiles), t = j % tiles;
   if (slab >= nslab) return;
   double* G = Gp + (long long)slab * ne.CB * ncols;
   // (Dl, Xs, sep_rows: one rank, round 5 -- the separators' share of E^T C^-1 E that is not in E_S^T X_S, (R_S - E_S)^T X_S over the compact
   // separator arrays, as further rows of K; with it the product may read the interiors' UNCORRECTED solutions: HipSchur, where ncorr is set)
-  if (t < nsym) {
-    int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
-    while (bi * (bi + 1) / 2 > t) --bi;
-    const int bj = t - bi * (bi + 1) / 2;
-    schur_gemm_tile<3>(ne, ncols, Ecm, Z, G, bi * kGemmT, bj * kGemmT, row_lo, row_hi, slab, nslab, red, Dl, Xs, sep_rows);
-  } else {
-    schur_gemm_tile<1>(ne, ncols, Ecm, Z, G, (t - nsym) * kGemmT, ne.CB, row_lo, row_hi, slab, nslab, red, Dl, Xs, sep_rows);
-  }
+  int bi, bj;
+  gemm_tile_decode(t, bi, bj);
+  if (bi == bj) schur_gemm_tile<4>(ne, ncols, Ecm, Z, G, bi * kGemmT, bj * kGemmT, row_lo, row_hi, slab, nslab, red, Dl, Xs, sep_rows);
+  else schur_gemm_tile<3>(ne, ncols, Ecm, Z, G, bi * kGemmT, bj * kGemmT, row_lo, row_hi, slab, nslab, red, Dl, Xs, sep_rows);
 }
 
 // S = (A + lambda D_c) - sum_slabs Gp[:, :CB] (dense CB x CB, both triangles from the computed lower block triangle),
@@ -2227,7 +2237,7 @@ __global__ __launch_bounds__(kFinThreads) void k_schur_finish(NEView ne, int nco
 #pragma unroll
   for (int q = 0; q < kRowsPer; ++q) {
     const int a = blockIdx.y * kNB + r0 + kRowStep * q;
-    const int hi = a / kGemmT >= b / kGemmT ? a : b, lo = a / kGemmT >= b / kGemmT ? b : a;
+    const int hi = a / 16 >= b / 16 ? a : b, lo = a / 16 >= b / 16 ? b : a;      // (k_schur_gemm computes the 16x16 sub-blocks on or below the diagonal)
     goff[q] = (a < ne.CB && b < ne.CB) ? (long long)hi * ncols + lo : -1;
     gsum[q] = 0.0;
   }

@@ -85,24 +85,11 @@ struct HipSchur {
   bool wide = false;                           // band wider than six control points: the general band kernels instead of the partitioned solver
   size_t win_lds = 0;
 
-  // K-slabs of the Schur product: a slab's tiles run on one XCD, two workgroups per CU, so the time is (rounds of the busiest XCD's
-  // slots) x (row sets per wavefront); the slab count with the least of that (ties: fewer slabs = fewer partial sums for k_schur_finish)
+  // K-slabs of the Schur product: the cost model of ba_gemm_plan.h for this device's CU count (MVUS_GEMM_SLABS: a forced count)
   void plan_gemm(int rows) {
-    const int nbk = (ne.CB + kGemmT - 1) / kGemmT, tiles = nbk * (nbk + 1) / 2 + nbk;
     int cus = 256;
     { int dev = 0; hipDeviceProp_t pr{}; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount; }
-    const int slots = 2 * cus, nsets = std::max(1, (rows + kGemmSetRows - 1) / kGemmSetRows);
-    nslab = 1;
-    if (sw.gemm_slabs > 0) nslab = sw.gemm_slabs;
-    else {
-      double best = 1e300;
-      for (int s = 1; s <= 128 && 4 * s <= nsets; ++s) {
-        const int per_wave = (nsets + 4 * s - 1) / (4 * s);                       // sets of the busiest wavefront
-        const int on_xcd = tiles * ((s + 7) / 8);                                 // workgroups of the busiest XCD
-        const double cost = (double)((on_xcd + slots / 8 - 1) / (slots / 8)) * (per_wave + 1.5) + 0.002 * s;
-        if (cost < best * 0.995) { best = cost; nslab = s; }
-      }
-    }
+    nslab = gemm_plan_slabs(ne.CB, rows, cus, sw.gemm_slabs);
   }
 
   explicit HipSchur(BE& b) : own(b), be(b), sw(read_switches()) {
@@ -789,12 +776,11 @@ struct HipSchur {
   }
   // G = E Z over the owned rows, in nslab partial sums
   void schur_product() {
-    const int nbk = (ne.CB + kGemmT - 1) / kGemmT;
     const bool corr = !wide && ncorr > 0;
     // the separators whose R_S^T X_S this rank adds: all of them, or -- time shard -- its own (global numbers q_off ...)
     // (two levels: plus the ghost -- the cut separator's correction term splits into the two neighbours' own parts of R_S)
     const int cq0 = shard ? pv.q_off - (two_level ? has_ghost : 0) : 0, cqn = shard ? n_own_sep + (two_level ? has_ghost : 0) : pv.m;
-    hipLaunchKernelGGL(k_schur_gemm, dim3(8 * (nbk * (nbk + 1) / 2 + nbk) * ((nslab + 7) / 8)), dim3(256), 0, be.stream, ne, ncols, 3 * own_lo, 3 * own_hi, nslab, ne.Et, Z, G,
+    hipLaunchKernelGGL(k_schur_gemm, dim3(gemm_grid(ne.CB, nslab)), dim3(256), 0, be.stream, ne, ncols, 3 * own_lo, 3 * own_hi, nslab, ne.Et, Z, G,
                        corr ? (const double*)(pv.Dl + (size_t)cq0 * pv.s3 * ne.CB) : (const double*)nullptr, (const double*)(pv.R + (size_t)cq0 * pv.s3 * ncols),
                        corr ? cqn * pv.s3 : 0);
   }
