@@ -74,9 +74,34 @@ void with_flag(bool on, F&& fn) {
   else fn(std::false_type{});
 }
 
+// Device memory, pinned host memory and events, recorded as they are taken and given back by reset() / the destructor: the one place
+// in the library that allocates and frees them.  Every taker makes room in its list first, so nothing can throw between taking and
+// recording.  It never synchronises: whoever frees while work may still be running synchronises first.
+struct DeviceOwner {
+  std::vector<void*> dev, host;
+  std::vector<hipEvent_t> events;
+  DeviceOwner() = default;
+  DeviceOwner(const DeviceOwner&) = delete;
+  DeviceOwner& operator=(const DeviceOwner&) = delete;
+  template <class T> static size_t bytes(size_t count) { return std::max<size_t>(count, 1) * sizeof(T); }
+  template <class T> T* device(size_t count) { dev.reserve(dev.size() + 1); void* p = nullptr; MVUS_HIP(hipMalloc(&p, bytes<T>(count))); dev.push_back(p); return static_cast<T*>(p); }
+  template <class T> T* mapped(size_t count) { return static_cast<T*>(host_alloc(bytes<T>(count), hipHostMallocMapped)); }
+  template <class T> T* pinned(size_t count) { return static_cast<T*>(host_alloc(bytes<T>(count), hipHostMallocDefault)); }
+  void* host_alloc(size_t size, unsigned flags) { host.reserve(host.size() + 1); void* p = nullptr; MVUS_HIP(hipHostMalloc(&p, size, flags)); host.push_back(p); return p; }
+  hipEvent_t event(unsigned flags = hipEventDefault) { events.reserve(events.size() + 1); hipEvent_t e = nullptr; MVUS_HIP(hipEventCreateWithFlags(&e, flags)); events.push_back(e); return e; }
+  bool empty() const { return dev.empty() && host.empty() && events.empty(); }
+  void reset() {
+    for (void* p : dev) (void)hipFree(p);
+    for (void* p : host) (void)hipHostFree(p);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    dev.clear(); host.clear(); events.clear();
+  }
+  ~DeviceOwner() { reset(); }
+};
+
 // device buffers and the stream of one stateless call, freed on every exit
 struct CallBuffers {
-  std::vector<void*> bufs;
+  DeviceOwner bufs;
   hipStream_t st = nullptr;
   void open(int device) {
     int ndev = 0;
@@ -85,10 +110,10 @@ struct CallBuffers {
     MVUS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   }
   template <class T>
-  T* get(size_t count) { void* p = nullptr; MVUS_HIP(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T))); bufs.push_back(p); return static_cast<T*>(p); }
+  T* get(size_t count) { return bufs.device<T>(count); }
   template <class T>
   T* put(const T* host, size_t count) { T* d = get<T>(count); if (count) MVUS_HIP(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, st)); return d; }
-  ~CallBuffers() { for (void* p : bufs) (void)hipFree(p); if (st) (void)hipStreamDestroy(st); }
+  ~CallBuffers() { bufs.reset(); if (st) (void)hipStreamDestroy(st); }
 };
 
 inline dim3 fit_blocks(long long cnt) { return dim3((unsigned)((cnt + 255) / 256)); }      // one thread per item, 256 a workgroup

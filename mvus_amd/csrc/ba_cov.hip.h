@@ -292,7 +292,7 @@ struct CovResult { double sigma2 = 0.0; int64_t dof = 0; };
 template <class BE>
 struct CovChain {
   BE& be;
-  std::vector<void*> dev;
+  DeviceOwner own;                 // the buffers and the stage events: regrown together (ensure)
   hipEvent_t ev[kCovStages + 1] = {};
   double stage_ms[kCovStages] = {};
   bool timed = false;
@@ -303,22 +303,10 @@ struct CovChain {
   int32_t *map = nullptr, *inv = nullptr;
   int* flags = nullptr;
   explicit CovChain(BE& b) : be(b) {}
-  CovChain(const CovChain&) = delete;
-  ~CovChain() {
-    for (void* p : dev) (void)hipFree(p);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
-  template <class T> T* device(size_t count) {
-    dev.reserve(dev.size() + 1);
-    void* p = nullptr;
-    MVUS_HIP(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-    dev.push_back(p);
-    return static_cast<T*>(p);
-  }
+  template <class T> T* device(size_t count) { return own.device<T>(count); }
   void ensure(const NEView& ne, int bw) {
     if (Lb && N3 == ne.N3 && CB == ne.CB && BW == bw) return;
-    for (void* p : dev) (void)hipFree(p);
-    dev.clear(); Lb = nullptr;
+    own.reset(); Lb = nullptr;
     N3 = ne.N3; CB = ne.CB; BW = bw;
     const size_t n3 = (size_t)N3, cb = (size_t)CB;
     diag = device<double>(cb + n3); est = device<uint8_t>(cb + n3);
@@ -328,8 +316,8 @@ struct CovChain {
     Rb = device<double>((size_t)ne.N * 36); sel = device<double>((size_t)ne.N * 36); band_out = device<double>((size_t)ne.N * 36);
     cam_out = device<double>(cb * cb);
     flags = device<int>(3);                                  // [0] band, [1] reduced camera system: first refused pivot; [2] k_band_chol_generic's own word (unused)
-    Lb = device<double>(n3 * (size_t)(bw + 1));
-    for (hipEvent_t& e : ev) if (!e) MVUS_HIP(hipEventCreate(&e));
+    for (hipEvent_t& e : ev) e = own.event();
+    Lb = device<double>(n3 * (size_t)(bw + 1));               // (last: a non-null Lb says that everything above exists)
   }
   void mark(int s) { MVUS_HIP(hipEventRecord(ev[s], be.stream)); }
 

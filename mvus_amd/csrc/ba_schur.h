@@ -30,7 +30,7 @@
 //                   bool retry_same();   after a failed solve: true = not a numerical failure, repeat it at the same lambda
 //                   bool spec_ok(jac_mode); void linearize_spec(B&, x, f, jac_mode); void adopt_spec(); void drop_spec();   the linearisation at a TRIAL point,
 //                                        enqueued into a second set of blocks before the host knows whether the trial is accepted
-// Backend additions: set_bounds(lb, ub) -> lb_ptr()/ub_ptr(); lm_scalars() (>= 8 doubles); dot_m_into(a, b, out);
+// Backend additions: set_bounds(lb, ub) -> lb_ptr()/ub_ptr(); lm_scalars() (LmSlot: kLmSlots doubles, kLmFailSum without a time shard's failure sums); dot_m_into(a, b, out);
 //                   lm_gnorm(x, lb, ub, g, out); lm_trial(x, p, lb, ub, g, D, fail, x_new, out4, gnorm_out) (the trial
 //                   kernel reads x, g and the bounds anyway, so it also delivers the gradient norm); fetch(src, k, host).
 #pragma once
@@ -43,6 +43,22 @@
 #include "ba_solver.h"
 
 namespace mvus {
+
+// The LM driver's scalars: what stands where in the block the backend hands out as lm_scalars().  One fetch of the head of the block
+// brings everything the host decides on; the trial kernel writes its four sums at kLmGradStep and |p|^2 behind the trial cost.
+enum LmSlot : int {
+  kLmCostX0 = 0,      // |f|^2 at x0
+  kLmGnorm,           // projected |g|_inf
+  kLmGradStep,        // g . step              } the four trial scalars, in the order k_lm_trial / lm_trial_host write them
+  kLmStepDStep,       // step^T D step         }
+  kLmStepSq,          // |step|^2              }
+  kLmXSq,             // |x|^2                 }
+  kLmTrialCost,       // |f(x_trial)|^2
+  kLmStepPSq,         // |p|^2 of the damped step before the trust region cuts it (lm_trust_radius)
+  kLmFailSum,         // [2] a time shard's failure flags summed over the ranks, fetched with the trial's scalars
+  kLmSlots = kLmFailSum + 2
+};
+static_assert(kLmStepPSq - kLmGradStep == 5, "k_lm_trial writes |p|^2 at out[5] of the trial scalars");
 
 // host restatements of the two small vector kernels (used by the host test backend; the HIP backend has kernels)
 // projected gradient: a component pushing against an active bound does not count
@@ -93,12 +109,11 @@ SolveResult lm_schur(B& be, Schur& sc, double* x, const std::vector<double>& lb,
   double* x_dev = be.lm_xbuf(xcur);
   double* xt_dev = be.lm_xbuf(xcur ^ 1);
   double* f_new = pool.get(m);
-  auto cleanup = [] {};
   be.set_bounds(lb, ub);
   const double* lbp = be.lb_ptr();
   const double* ubp = be.ub_ptr();
-  double* S = be.lm_scalars();   // [0] |f|^2 at x0, [1] projected |g|_inf, [2..5] trial scalars, [6] |f(x_trial)|^2
-  double hs[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double* S = be.lm_scalars();   // indexed by LmSlot
+  double hs[kLmSlots] = {};
 
   if (!resumed) be.upload(x_dev, x, n);
   // A resumed point may come with more than its coordinates: the previous solve left f(x) in the residual buffer (its last accepted
@@ -109,7 +124,7 @@ SolveResult lm_schur(B& be, Schur& sc, double* x, const std::vector<double>& lb,
   bool cost_known = false;
   // (the first linearisation follows at once: its storage is zeroed beside this evaluation where the backend can do that)
   if (carry.f_valid) { cost = carry.cost; res.initial_cost = cost; cost_known = true; }
-  else if (be.residual_sq(x_dev, f_dev, S, sc.clear_ptr(), sc.clear_len())) sc.mark_cleared();
+  else if (be.residual_sq(x_dev, f_dev, S + kLmCostX0, sc.clear_ptr(), sc.clear_len())) sc.mark_cleared();
   res.nfev = 1; res.njev = 1;
   if (!(carry.f_valid && carry.lin_valid)) sc.linearize(be, x_dev, f_dev, opt.jac_mode, true);
   bool lin_at_x = true;                 // the blocks the solver holds are those of x_dev
@@ -125,19 +140,19 @@ SolveResult lm_schur(B& be, Schur& sc, double* x, const std::vector<double>& lb,
   try {
   // Trust region in the reference's metric (mvus_solve_opts.lm_trust_radius): scipy's TRF with x_scale = 1 bounds |step|_2 by Delta
   // (scipy/optimize/_lsq/trf.py: Delta_0 = |x0|, or 1 when that is 0) and updates it with update_tr_radius (_lsq/common.py).  The
-  // damped step p(lambda) is cut back to Delta along its direction by the trial kernel; S[7] brings |p|^2 back.
+  // damped step p(lambda) is cut back to Delta along its direction by the trial kernel; S[kLmStepPSq] brings |p|^2 back.
   const bool tr = opt.lm_trust_radius >= 0;
   double Delta = 0;
   if (tr) {
     Delta = opt.lm_trust_radius;
     if (!(Delta > 0)) { double s2 = 0; for (int64_t i = 0; i < n; ++i) s2 += x[i] * x[i]; Delta = s2 > 0 ? std::sqrt(s2) : 1.0; }
   }
-  const int nfetch_all = sc.fail_in_scalars() ? 10 : (tr ? 8 : 7);      // (time shards: + the solve's failure flags, summed over the ranks)
+  const int nfetch_all = sc.fail_in_scalars() ? kLmSlots : (tr ? kLmStepPSq + 1 : kLmTrialCost + 1);      // (time shards: + the solve's failure flags, summed over the ranks)
   auto launch_trial = [&](double lambda) {
     sc.solve_async(lambda, true);
-    be.lm_trial(x_dev, sc.step_ptr(), lbp, ubp, sc.grad_ptr(), sc.diag_ptr(), sc.fail_ptr(), xt_dev, S + 2, S + 1, be.mirror_dev(mir_trial),
-                tr ? S + 7 : nullptr, Delta, sc.fail_sum_ptr());
-    be.residual_sq(xt_dev, f_new, S + 6);
+    be.lm_trial(x_dev, sc.step_ptr(), lbp, ubp, sc.grad_ptr(), sc.diag_ptr(), sc.fail_ptr(), xt_dev, S + kLmGradStep, S + kLmGnorm, be.mirror_dev(mir_trial),
+                tr ? S + kLmStepPSq : nullptr, Delta, sc.fail_sum_ptr());
+    be.residual_sq(xt_dev, f_new, S + kLmTrialCost);
     // Most trials are accepted, and an accepted trial is followed by the linearisation at its point: that linearisation is enqueued NOW,
     // into the solver's second set of blocks, behind a marker the fetch below waits for instead of the whole stream -- the GPU works on
     // it while the host wakes up, decides and enqueues the next solve (20 - 60 us of idle device per iteration otherwise).  A rejected
@@ -154,24 +169,24 @@ SolveResult lm_schur(B& be, Schur& sc, double* x, const std::vector<double>& lb,
   while (true) {
     const bool can_try = res.nfev < opt.max_nfev;
     if (can_try) launch_trial(lambda);             // speculative: dropped if the gradient test below ends the solve
-    else be.lm_gnorm(x_dev, lbp, ubp, sc.grad_ptr(), S + 1);
-    be.fetch(S, can_try ? nfetch : 2, hs);
+    else be.lm_gnorm(x_dev, lbp, ubp, sc.grad_ptr(), S + kLmGnorm);
+    be.fetch(S, can_try ? nfetch : kLmGnorm + 1, hs);
     if (!cost_known) {
-      cost = 0.5 * hs[0];
-      if (!std::isfinite(cost)) { res.error = -3; cleanup(); return res; }
+      cost = 0.5 * hs[kLmCostX0];
+      if (!std::isfinite(cost)) { res.error = -3; return res; }
       res.initial_cost = cost;
       cost_known = true;
     }
-    g_norm = hs[1];
+    g_norm = hs[kLmGnorm];
     if (g_norm < opt.gtol) status = 1;
     if (status != -1 || !can_try) break;
 
     double actual_reduction = -1, cost_new = cost;
     bool have_trial = true;
     while (actual_reduction <= 0 && res.nfev < opt.max_nfev) {
-      if (!have_trial) { launch_trial(lambda); be.fetch(S + 2, nfetch - 2, hs + 2); }
+      if (!have_trial) { launch_trial(lambda); be.fetch(S + kLmGradStep, nfetch - kLmGradStep, hs + kLmGradStep); }
       have_trial = false;
-      if (!sc.solve_ok() || !std::isfinite(hs[2]) || !std::isfinite(hs[3])) {   // not positive definite at this damping: raise it
+      if (!sc.solve_ok() || !std::isfinite(hs[kLmGradStep]) || !std::isfinite(hs[kLmStepDStep])) {   // not positive definite at this damping: raise it
         if (spec_live) { sc.drop_spec(); spec_live = false; }
         if (sc.retry_same()) continue;      // (not a numerical failure -- an in-launch hand-over timed out: the same solve again, other route)
         lambda *= 10.0;
@@ -181,15 +196,15 @@ SolveResult lm_schur(B& be, Schur& sc, double* x, const std::vector<double>& lb,
       ++res.lin_iters;
       // predicted reduction of the quadratic model: -(g.p + 0.5 p^T H p) = 0.5 (lambda p^T D p - g.p)
       // (a step cut back to the trust region, st = cut p: -g.st - st^T H st / 2 with p^T H p = -g.p - lambda p^T D p)
-      const double cut = (tr && hs[7] > Delta * Delta) ? Delta / std::sqrt(hs[7]) : 1.0;
-      const double predicted = cut < 1.0 ? 0.5 * lambda * hs[3] - (1.0 - 0.5 * cut) * hs[2] : 0.5 * (lambda * hs[3] - hs[2]);
+      const double cut = (tr && hs[kLmStepPSq] > Delta * Delta) ? Delta / std::sqrt(hs[kLmStepPSq]) : 1.0;
+      const double predicted = cut < 1.0 ? 0.5 * lambda * hs[kLmStepDStep] - (1.0 - 0.5 * cut) * hs[kLmGradStep] : 0.5 * (lambda * hs[kLmStepDStep] - hs[kLmGradStep]);
       ++res.nfev;
-      cost_new = 0.5 * hs[6];
+      cost_new = 0.5 * hs[kLmTrialCost];
       if (!std::isfinite(cost_new)) { if (spec_live) { sc.drop_spec(); spec_live = false; } lambda *= nu; nu *= 2.0; continue; }
       actual_reduction = cost - cost_new;
       const double ratio = predicted > 0 ? actual_reduction / predicted : (actual_reduction > 0 ? 1.0 : 0.0);
-      const double step_norm = std::sqrt(hs[4]);
-      const int term = check_termination(actual_reduction, cost, step_norm, std::sqrt(hs[5]), ratio, opt.ftol, opt.xtol);
+      const double step_norm = std::sqrt(hs[kLmStepSq]);
+      const int term = check_termination(actual_reduction, cost, step_norm, std::sqrt(hs[kLmXSq]), ratio, opt.ftol, opt.xtol);
       if (opt.verbose >= 2)
         std::fprintf(stderr, "lm: nfev=%d cost=%.10e -> %.10e lambda=%.3e ratio=%.3f |step|=%.3e\n", res.nfev, cost, cost_new, lambda, ratio, step_norm);
       const double lambda_used = lambda;
@@ -209,7 +224,7 @@ SolveResult lm_schur(B& be, Schur& sc, double* x, const std::vector<double>& lb,
         // a step that had to be cut to less than half: the next damped step should come out near the radius by itself (its
         // direction then turns from Gauss-Newton's towards the scaled gradient, as the exact trust-region step does)
         if (cut < 0.5) lambda = std::max(lambda, std::min(lambda_used * 0.5 / cut, lambda_used * 10.0));
-        if (opt.verbose >= 2) std::fprintf(stderr, "lm:   trust region: |p|=%.3e cut=%.3f Delta -> %.3e\n", std::sqrt(hs[7]), cut, Delta);
+        if (opt.verbose >= 2) std::fprintf(stderr, "lm:   trust region: |p|=%.3e cut=%.3f Delta -> %.3e\n", std::sqrt(hs[kLmStepPSq]), cut, Delta);
       }
       if (term != -1) { status = term; break; }
     }
@@ -233,9 +248,9 @@ SolveResult lm_schur(B& be, Schur& sc, double* x, const std::vector<double>& lb,
       else sc.linearize(be, x_dev, f_dev, opt.jac_mode, true);
     }
     if (status != -1) {                 // converged / gave up: report the gradient norm of the final linearisation
-      be.lm_gnorm(x_dev, lbp, ubp, sc.grad_ptr(), S + 1);
-      be.fetch(S + 1, 1, hs + 1);
-      g_norm = hs[1];
+      be.lm_gnorm(x_dev, lbp, ubp, sc.grad_ptr(), S + kLmGnorm);
+      be.fetch(S + kLmGnorm, 1, hs + kLmGnorm);
+      g_norm = hs[kLmGnorm];
       break;
     }
   }
@@ -256,7 +271,6 @@ SolveResult lm_schur(B& be, Schur& sc, double* x, const std::vector<double>& lb,
   be.lm_remember(x_dev, x, mir_cur >= 0 ? be.mirror_host(mir_cur) : nullptr);
   if (!res.error) be.lm_keep(LmCarry{true, lin_at_x, cost}, opt.jac_mode);      // f_dev holds f(x_dev) on every regular exit
   res.cost = cost;
-  cleanup();
   return res;
 }
 

@@ -12,13 +12,13 @@ template <class BE>
 struct SchurOwner {
   BE& be;
   std::vector<double*> pool;
-  std::vector<void*> dev, pinned;
+  DeviceOwner mem;
   explicit SchurOwner(BE& b) : be(b) {}
-  SchurOwner(const SchurOwner&) = delete;      // (alloc & co. make room in their list first: nothing throws between taking and recording)
+  SchurOwner(const SchurOwner&) = delete;      // (alloc makes room in its list first, like DeviceOwner: nothing throws between taking and recording)
   double* alloc(size_t len) { pool.reserve(pool.size() + 1); pool.push_back(be.alloc((int64_t)len)); return pool.back(); }
-  template <class T> T* device(size_t count) { dev.reserve(dev.size() + 1); void* p = nullptr; MVUS_HIP(hipMalloc(&p, count * sizeof(T))); dev.push_back(p); return static_cast<T*>(p); }
-  template <class T> T* mapped(size_t count) { pinned.reserve(pinned.size() + 1); void* p = nullptr; MVUS_HIP(hipHostMalloc(&p, count * sizeof(T), hipHostMallocMapped)); pinned.push_back(p); return static_cast<T*>(p); }
-  ~SchurOwner() { for (double* p : pool) be.release(p); for (void* p : dev) (void)hipFree(p); for (void* p : pinned) (void)hipHostFree(p); }
+  template <class T> T* device(size_t count) { return mem.device<T>(count); }
+  template <class T> T* mapped(size_t count) { return mem.mapped<T>(count); }
+  ~SchurOwner() { for (double* p : pool) be.release(p); }
 };
 
 // column batch and dynamic LDS of k_sep_bcr_rhs for a chain of m separators: kBcrCols columns per workgroup, one where they exceed 64 KB

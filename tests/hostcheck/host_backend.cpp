@@ -53,7 +53,7 @@ struct HostBackend {
   double dot_m(const double* a, const double* b) { return dot_n(a, b, hp.m); }
   // device-resident LM driver (ba_schur.h): host memory plays the role of device memory
   std::vector<double> lbv, ubv;
-  double lm_s[8];
+  double lm_s[mvus::kLmFailSum];      // the LM driver's block without the failure sums (HostSchur::fail_in_scalars is false)
   void set_bounds(const std::vector<double>& lb, const std::vector<double>& ub) { lbv = lb; ubv = ub; }
   const double* lb_ptr() const { return lbv.data(); }
   const double* ub_ptr() const { return ubv.data(); }

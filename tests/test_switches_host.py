@@ -22,7 +22,7 @@ TABLE = {
 }
 # read outside the table, by design: the roctx ranges of api_common.h and the spline unit's own switches (MVUS_DEBUG there is the table's name)
 OUTSIDE = {'MVUS_ROCTX', 'MVUS_BAND_PARTS_SCALE', 'MVUS_FIT_SLICES_MAX', 'MVUS_BAND_PARTS_MIN', 'MVUS_FIT_TIMING', 'MVUS_DEBUG'}
-BA_FILES = ('ba_api.hip', 'ba_schur_host.hip.h', 'ba_schur.h', 'ba_solver.h')
+BA_FILES = ('ba_api.hip', 'ba_backend.hip.h', 'ba_schur_host.hip.h', 'ba_schur.h', 'ba_solver.h')
 
 
 @pytest.fixture
