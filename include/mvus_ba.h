@@ -499,6 +499,29 @@ int mvus_spline_fit_open(int32_t device, int64_t m, const double* u, const doubl
 int mvus_spline_fit_smooth(mvus_spline_fit* fit, double s, int32_t* n_out, double* t_out, double* c_out, double* fp_out, int32_t* ier_out);
 void mvus_spline_fit_close(mvus_spline_fit* fit);
 
+/* The banded solvers of that fit on a system handed in: inspection hooks for k_band_solve, k_band_solve_parts and k_band_diag_sum
+ * (spline_fit.hip.h), as mvus_ba_lm_step is for the Schur chain.  No reference counterpart.
+ *   G5[5*n], BtB[5*n]: the kernels' lower-band layout, M(j, j - w) at 5 j + w, w = 0..4; entries with j - w < 0 must be 0.
+ *   rhs[3*n], c_out[3*n]: column d at d * n + j.
+ *   G5_lo, BtB_lo, rhs_lo: NULL, or the low words of the operands; read only when precise != 0, where the kernels run in
+ *   double-double on dd(hi, lo).  precise == 0: fp64 on the high words.
+ *   hb == 3: solves G5 x = rhs as a least-squares pass does (G5's w = 4 column is not read); BtB, BtB_lo must be NULL.
+ *   hb == 4: solves (G5 + pinv^2 BtB) x = rhs as a smoothing pass does, through the same combine kernel.
+ *   parts == -1: one chain (k_band_solve).  parts == 0: the fit's own rule (from 192 rows on: about sqrt(n / 2.5) interiors,
+ *   k_band_solve_parts).  parts >= 2: exactly that many interiors.  *P_out = the number of interiors used (1: one chain).
+ *   stats_out[4] = what the kernel leaves in out[0..3]: [0] the sum of diag(L) (NaN from the partitioned kernel, which does not form
+ *   it), [1] NaN, [2], [3] the smallest and largest Cholesky pivot (square roots) in the kernel's own elimination order.
+ *   *fail_out = 1 when a pivot fell below 1e-12 (fp64) / 1e-24 (double-double) of its diagonal entry and was floored.
+ * The work arrays are sized by the fit's own rule for exactly n coefficients.  MVUS_E_INVALID, before any launch: n < 4, hb not 3 or 4, a NULL pointer
+ * other than the _lo ones, BtB with hb == 3, no BtB or a non-finite pinv with hb == 4, parts < -1 or 1, parts > 256 or an interior
+ * shorter than 2 hb rows ((n - (parts - 1) hb) / parts < 2 hb).  Stateless; no CPU fallback. */
+int mvus_spline_band_solve(int32_t device, int32_t n, int32_t hb, int32_t precise, int32_t parts, const double* G5, const double* G5_lo,
+                           const double* BtB, const double* BtB_lo, double pinv, const double* rhs, const double* rhs_lo, double* c_out,
+                           double* stats_out, int32_t* fail_out, int32_t* P_out);
+/* out[0] = the sum of diag(L) of G5 = L L^T (hb = 3) in the natural order, by k_band_diag_sum: fppara's initial p after a partitioned
+ * pass.  Arguments as above.  MVUS_E_INVALID: n < 4, G5 or out NULL. */
+int mvus_spline_band_diag_sum(int32_t device, int32_t n, int32_t precise, const double* G5, const double* G5_lo, double* out);
+
 /* Scene.get_camera_pose's cv2.solvePnPRansac(objectPoints, imagePoints, K, d, reprojectionError=error) (common.py:744; OpenCV is
  * a third-party dependency absent from this image: parity unpinned, see pnp.hip.h).  X[3*N] object points (x(N) y(N) z(N)),
  * uv[2*N] raw pixels (u(N) v(N)), K = fx fy cx cy, d = k1 k2 p1 p2 k3.  `iterations` hypotheses (OpenCV's iterationsCount,

@@ -36,14 +36,17 @@ static int band_parts_min() {
 }
 // banded solve of the pass; returns true when the factor's diagonal in out[0] is FITPACK's (one chain in the natural order)
 template <int HB, class T>
-static bool fit_band_solve(hipStream_t st, FitWork<T>& w, int ncoef, const T* Mband, double* cd, double* out, int* fail) {
-  const BandParts bp = band_parts(ncoef, HB, band_parts_min());
+static bool fit_band_solve(hipStream_t st, FitWork<T>& w, int ncoef, const BandParts& bp, const T* Mband, double* cd, double* out, int* fail) {
   if (bp.P < 2) {
     hipLaunchKernelGGL((k_band_solve<HB, T>), dim3(1), dim3(64), 0, st, ncoef, Mband, w.rhs, w.Lf, w.yw, cd, out, fail);
     return true;
   }
   hipLaunchKernelGGL((k_band_solve_parts<HB, T>), dim3(1), dim3(64 * ((bp.P + 63) / 64)), 0, st, ncoef, bp, Mband, w.rhs, w.Lf, w.yw, w.YL, w.parts, cd, out, fail);
   return false;
+}
+template <int HB, class T>
+static bool fit_band_solve(hipStream_t st, FitWork<T>& w, int ncoef, const T* Mband, double* cd, double* out, int* fail) {
+  return fit_band_solve<HB, T>(st, w, ncoef, band_parts(ncoef, HB, band_parts_min()), Mband, cd, out, fail);
 }
 // least-squares spline on the current knots: normal equations from the span blocks, banded Cholesky, coefficients -> cd
 template <class T>
@@ -69,6 +72,67 @@ static void fit_smooth_pass(hipStream_t st, FitWork<T>& w, int ncoef, int n8, co
   hipLaunchKernelGGL(k_fit_combine<T>, fit_blocks(5ll * ncoef), dim3(256), 0, st, 5ll * ncoef, w.G5, w.BtB, pinv, w.Mx, ncoef, w.rhs,
                      band_parts(ncoef, 4, band_parts_min()), w.Lf, w.yw);
   fit_band_solve<4, T>(st, w, ncoef, w.Mx, cd, out, fail);
+}
+
+// ---- inspection: the band solvers on a system handed in (mvus_spline_band_solve, mvus_spline_band_diag_sum) ----------------------------
+// `count` operands on the device as T: the high words alone in fp64, dd(hi, lo) in double-double (lo NULL: 0).  `stage` outlives the copy.
+static void band_fill(CallBuffers& cb, double* dst, const double* hi, const double*, size_t count, std::vector<dd>&) {
+  MVUS_HIP(hipMemcpyAsync(dst, hi, sizeof(double) * count, hipMemcpyHostToDevice, cb.st));
+}
+static void band_fill(CallBuffers& cb, dd* dst, const double* hi, const double* lo, size_t count, std::vector<dd>& stage) {
+  stage.resize(count);
+  for (size_t i = 0; i < count; ++i) stage[i] = dd(hi[i], lo ? lo[i] : 0.0);
+  MVUS_HIP(hipMemcpyAsync(dst, stage.data(), sizeof(dd) * count, hipMemcpyHostToDevice, cb.st));
+}
+// the work arrays of a fit with nest = n (FitWork::alloc: the allocation rule is what the kernels index into), the system copied in, then
+// what fit_lsq_pass (hb = 3) / fit_smooth_pass (hb = 4) launch after their assembly
+template <class T>
+static int band_solve_run(int32_t device, int n, int hb, const BandParts& bp, const double* G5, const double* G5_lo, const double* BtB, const double* BtB_lo,
+                          double pinv, const double* rhs, const double* rhs_lo, double* c_out, double* stats_out, int32_t* fail_out) {
+  CallBuffers cb;
+  cb.open(device);
+  FitWork<T> w;
+  w.alloc(cb, (size_t)n);
+  std::vector<dd> s_g, s_b, s_r;
+  band_fill(cb, w.G5, G5, G5_lo, 5 * (size_t)n, s_g);
+  band_fill(cb, w.rhs, rhs, rhs_lo, 3 * (size_t)n, s_r);
+  if (hb == 4) band_fill(cb, w.BtB, BtB, BtB_lo, 5 * (size_t)n, s_b);
+  double* cd = cb.get<double>(3 * (size_t)n);
+  double* out = cb.get<double>(4);
+  int* fail = cb.get<int>(1);
+  const double unset = std::nan("");
+  const double out0[4] = {unset, unset, unset, unset};       // out[0] stays NaN where the partitioned kernel does not write it
+  MVUS_HIP(hipMemcpyAsync(out, out0, sizeof(out0), hipMemcpyHostToDevice, cb.st));
+  MVUS_HIP(hipMemsetAsync(fail, 0, sizeof(int), cb.st));
+  if (hb == 3) {
+    if (bp.P > 1) hipLaunchKernelGGL(k_band_scatter<T>, fit_blocks(n), dim3(256), 0, cb.st, n, w.G5, w.rhs, bp, w.Lf, w.yw);
+    fit_band_solve<3, T>(cb.st, w, n, bp, w.G5, cd, out, fail);
+  } else {
+    hipLaunchKernelGGL(k_fit_combine<T>, fit_blocks(5ll * n), dim3(256), 0, cb.st, 5ll * n, w.G5, w.BtB, pinv, w.Mx, n, w.rhs, bp, w.Lf, w.yw);
+    fit_band_solve<4, T>(cb.st, w, n, bp, w.Mx, cd, out, fail);
+  }
+  MVUS_HIP(hipGetLastError());
+  int fh = 0;
+  MVUS_HIP(hipMemcpyAsync(c_out, cd, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipMemcpyAsync(stats_out, out, sizeof(double) * 4, hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipMemcpyAsync(&fh, fail, sizeof(int), hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipStreamSynchronize(cb.st));
+  *fail_out = fh;
+  return MVUS_OK;
+}
+template <class T>
+static int band_diag_sum_run(int32_t device, int n, const double* G5, const double* G5_lo, double* out_host) {
+  CallBuffers cb;
+  cb.open(device);
+  T* M = cb.get<T>(5 * (size_t)n);
+  std::vector<dd> s_g;
+  band_fill(cb, M, G5, G5_lo, 5 * (size_t)n, s_g);
+  double* out = cb.get<double>(1);
+  hipLaunchKernelGGL((k_band_diag_sum<3, T>), dim3(1), dim3(64), 0, cb.st, n, M, out);
+  MVUS_HIP(hipGetLastError());
+  MVUS_HIP(hipMemcpyAsync(out_host, out, sizeof(double), hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipStreamSynchronize(cb.st));
+  return MVUS_OK;
 }
 
 extern "C" {
@@ -539,6 +603,32 @@ int mvus_spline_smooth(int32_t device, int64_t m, const double* u, const double*
   const int rc = spline_fit_open_impl(S, device, m, u, X);
   if (rc != MVUS_OK) return rc;
   return spline_fit_run(S, s, n_out, t_out, c_out, fp_out, ier_out);
+}
+
+int mvus_spline_band_solve(int32_t device, int32_t n, int32_t hb, int32_t precise, int32_t parts, const double* G5, const double* G5_lo, const double* BtB,
+                           const double* BtB_lo, double pinv, const double* rhs, const double* rhs_lo, double* c_out, double* stats_out, int32_t* fail_out,
+                           int32_t* P_out) {
+  if (n < 4 || (hb != 3 && hb != 4) || !G5 || !rhs || !c_out || !stats_out || !fail_out || !P_out) { g_create_error = "spline_band_solve: bad arguments (n >= 4, hb 3 or 4)"; return MVUS_E_INVALID; }
+  if (hb == 3 && (BtB || BtB_lo)) { g_create_error = "spline_band_solve: hb = 3 solves G5 alone, BtB must be NULL"; return MVUS_E_INVALID; }
+  if (hb == 4 && (!BtB || !std::isfinite(pinv))) { g_create_error = "spline_band_solve: hb = 4 needs BtB and a finite pinv"; return MVUS_E_INVALID; }
+  if (parts < -1 || parts == 1 || (parts >= 2 && !band_parts_legal(n, hb, parts))) {
+    g_create_error = "spline_band_solve: parts must be -1 (one chain), 0 (the production rule) or 2..256 interiors of at least 2 hb rows";
+    return MVUS_E_INVALID;
+  }
+  BandParts bp;
+  bp.HB = hb;
+  if (parts == 0) bp = band_parts(n, hb, 192);
+  else if (parts >= 2) bp = band_parts_fixed(n, hb, parts);
+  *P_out = bp.P;
+  return stateless([&] {
+    return precise ? band_solve_run<dd>(device, n, hb, bp, G5, G5_lo, BtB, BtB_lo, pinv, rhs, rhs_lo, c_out, stats_out, fail_out)
+                   : band_solve_run<double>(device, n, hb, bp, G5, G5_lo, BtB, BtB_lo, pinv, rhs, rhs_lo, c_out, stats_out, fail_out);
+  });
+}
+
+int mvus_spline_band_diag_sum(int32_t device, int32_t n, int32_t precise, const double* G5, const double* G5_lo, double* out) {
+  if (n < 4 || !G5 || !out) { g_create_error = "spline_band_diag_sum: bad arguments (n >= 4)"; return MVUS_E_INVALID; }
+  return stateless([&] { return precise ? band_diag_sum_run<dd>(device, n, G5, G5_lo, out) : band_diag_sum_run<double>(device, n, G5, G5_lo, out); });
 }
 
 }  // extern "C"

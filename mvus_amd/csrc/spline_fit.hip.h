@@ -91,19 +91,29 @@ struct BandParts {
   // so that the P lanes of k_band_solve_parts (one interior each) read and write consecutive addresses
   MVUS_HD long long at(int p, int i, int k, int K) const { return ((long long)i * K + k) * P + p; }
 };
+constexpr int kBandPartsMax = 256;
+// n rows can be cut into P interiors: one lane each (P <= kBandPartsMax), every interior at least 2 HB rows long
+inline bool band_parts_legal(int n, int HB, int P) { return P >= 2 && P <= kBandPartsMax && n > (P - 1) * HB && (n - (P - 1) * HB) / P >= 2 * HB; }
+// exactly P interiors (a legal P): the first rem of them have len + 1 rows, the others len
+inline BandParts band_parts_fixed(int n, int HB, int P) {
+  BandParts bp;
+  bp.HB = HB;
+  bp.P = P;
+  bp.len = (n - (P - 1) * HB) / P;
+  bp.rem = (n - (P - 1) * HB) - bp.len * P;
+  return bp;
+}
+// the production rule: one chain below min_rows, else about sqrt(n / 2.5) interiors of at least 2 HB rows
 inline BandParts band_parts(int n, int HB, int min_rows) {
   BandParts bp;
   bp.HB = HB;
   if (n < min_rows) return bp;
   static const double scale = [] { const char* e = std::getenv("MVUS_BAND_PARTS_SCALE"); return e ? std::atof(e) : 1.0; }();      // (experiments)
   int P = (int)(scale * std::sqrt((double)n / 2.5));
-  P = std::max(2, std::min(256, P));
+  P = std::max(2, std::min(kBandPartsMax, P));
   while (P > 1 && (n - (P - 1) * HB) / P < 2 * HB) --P;
   if (P < 2) return bp;
-  bp.P = P;
-  bp.len = (n - (P - 1) * HB) / P;
-  bp.rem = (n - (P - 1) * HB) - bp.len * P;
-  return bp;
+  return band_parts_fixed(n, HB, P);
 }
 #if defined(__HIPCC__)
 constexpr int kFitBlk = 22;      // per span: 10 products h_a h_b (a >= b) + 12 products h_a x_d
@@ -205,6 +215,20 @@ __global__ __launch_bounds__(256) void k_fit_slice_sum(long long count, int nsli
   SB[e] = v;
 }
 
+// row j of the normal equations (g[w] = M(j, j - w), w < 4) and of the right-hand sides into the copy k_band_solve_parts<3> reads
+// (see BandParts::at); separator rows have no place there
+template <class T>
+__device__ __forceinline__ void band_parts_scatter(const BandParts& bp, int j, const T* g, const T* r, T* __restrict__ Mt, T* __restrict__ rt) {
+  int p, i;
+  bp.locate(j, p, i);
+  if (i < bp.length(p)) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) Mt[bp.at(p, i, w, 4)] = g[w];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) rt[bp.at(p, i, d, 3)] = r[d];
+  }
+}
+
 // lower banded storage, width W = HB + 1: G[j * W + w] = M(j, j - w).  Here the normal equations in a width-5 array (w = 4
 // zero) so that the penalty can be added in place, and rhs[d * ncoef + j].
 template <class T>
@@ -225,16 +249,20 @@ __global__ __launch_bounds__(256) void k_fit_band(int ncoef, int nspan, const T*
   for (int w = 0; w < 5; ++w) G5[5 * (long long)j + w] = g[w];
 #pragma unroll
   for (int d = 0; d < 3; ++d) rhs[(long long)d * ncoef + j] = r[d];
-  if (bp.P > 1) {                                    // the copy k_band_solve_parts<3> reads (see BandParts::at)
-    int p, i;
-    bp.locate(j, p, i);
-    if (i < bp.length(p)) {
+  if (bp.P > 1) band_parts_scatter(bp, j, g, r, Mt, rt);
+}
+// the same copy from a system that is already in G5 / rhs (mvus_spline_band_solve with hb = 3: no span blocks to feed k_fit_band)
+template <class T>
+__global__ __launch_bounds__(256) void k_band_scatter(int ncoef, const T* __restrict__ G5, const T* __restrict__ rhs, BandParts bp, T* __restrict__ Mt,
+                                                      T* __restrict__ rt) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= ncoef) return;
+  T g[4], r[3];
 #pragma unroll
-      for (int w = 0; w < 4; ++w) Mt[bp.at(p, i, w, 4)] = g[w];
+  for (int w = 0; w < 4; ++w) g[w] = G5[5 * (long long)j + w];
 #pragma unroll
-      for (int d = 0; d < 3; ++d) rt[bp.at(p, i, d, 3)] = r[d];
-    }
-  }
+  for (int d = 0; d < 3; ++d) r[d] = rhs[(long long)d * ncoef + j];
+  band_parts_scatter(bp, j, g, r, Mt, rt);
 }
 
 // BtB[j * 5 + w] = (B^T B)(j, j - w) for the n8 x ncoef jump matrix B whose row `it` holds b[it * 5 + c] in column it + c
@@ -409,7 +437,6 @@ template <int HB> struct BandRec {                  // per interior (T units)
 template <int HB> struct BandSep {                  // per separator (T units): its Cholesky block, the coupling W to the next one, z, x
   static constexpr int LT = 0, W = HB * HB, Z = 2 * HB * HB, X = 2 * HB * HB + 3 * HB, SIZE = 2 * HB * HB + 6 * HB;
 };
-constexpr int kBandPartsMax = 256;
 constexpr int kBandPartsWork = kBandPartsMax * (BandRec<4>::SIZE + BandSep<4>::SIZE);        // T units of `work`
 
 template <class T>

@@ -227,6 +227,57 @@ class SmoothFit:
             pass
 
 
+def _band_operand(a, lo, shape, name):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError('%s has shape %s, expected %s' % (name, a.shape, shape))
+    if lo is not None:
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        if lo.shape != shape:
+            raise ValueError('%s_lo has shape %s, expected %s' % (name, lo.shape, shape))
+    return a, lo
+
+
+def band_solve(G5, rhs, hb, BtB=None, pinv=0.0, precise=False, parts=0, G5_lo=None, BtB_lo=None, rhs_lo=None, device=0):
+    """The fit's banded solvers on a system handed in (``mvus_spline_band_solve``, an inspection hook): G5[n, 5] (and BtB[n, 5] with
+    ``hb`` = 4) in the kernels' lower-band layout, ``M(j, j - w)`` at ``[j, w]``; rhs[3, n].  Solves G5 (hb = 3) or G5 + pinv^2 BtB
+    (hb = 4) in fp64, or in double-double on (hi, ``_lo``) when ``precise``; ``parts`` = -1 one chain, 0 the fit's own rule, >= 2 that
+    many interiors.  Returns a namespace: c[3, n], stats[4] (the kernel's out[0..3]), fail, P (interiors used)."""
+    from types import SimpleNamespace
+    lib = _lib.load()
+    G5 = np.ascontiguousarray(G5, dtype=np.float64)
+    n = G5.shape[0] if G5.ndim == 2 else -1
+    G5, G5_lo = _band_operand(G5, G5_lo, (n, 5), 'G5')
+    rhs, rhs_lo = _band_operand(rhs, rhs_lo, (3, n), 'rhs')
+    if BtB is not None:
+        BtB, BtB_lo = _band_operand(BtB, BtB_lo, (n, 5), 'BtB')
+    elif BtB_lo is not None:
+        raise ValueError('BtB_lo without BtB')
+    p = lambda a: _lib.dptr(a) if a is not None else None    # noqa: E731
+    c = np.zeros((3, max(n, 1)))
+    stats = np.zeros(4)
+    fail, P = ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = lib.mvus_spline_band_solve(int(device), int(n), int(hb), int(bool(precise)), int(parts), p(G5), p(G5_lo), p(BtB), p(BtB_lo), float(pinv),
+                                    p(rhs), p(rhs_lo), _lib.dptr(c), _lib.dptr(stats), ctypes.byref(fail), ctypes.byref(P))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_band_solve')
+    return SimpleNamespace(c=c, stats=stats, fail=fail.value, P=P.value)
+
+
+def band_diag_sum(G5, precise=False, G5_lo=None, device=0):
+    """Sum of diag(L) of G5 = L L^T (half-bandwidth 3) in the natural order, by the kernel that gives the smoothing iteration its initial
+    p after a partitioned pass (``mvus_spline_band_diag_sum``, an inspection hook).  G5[n, 5] as in ``band_solve``."""
+    lib = _lib.load()
+    G5 = np.ascontiguousarray(G5, dtype=np.float64)
+    n = G5.shape[0] if G5.ndim == 2 else -1
+    G5, G5_lo = _band_operand(G5, G5_lo, (n, 5), 'G5')
+    out = np.zeros(1)
+    rc = lib.mvus_spline_band_diag_sum(int(device), int(n), int(bool(precise)), _lib.dptr(G5), _lib.dptr(G5_lo) if G5_lo is not None else None, _lib.dptr(out))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_band_diag_sum')
+    return float(out[0])
+
+
 def _fprati(p1, f1, p2, f2, p3, f3):
     """FITPACK fprati: the zero of the rational interpolant r(p) = (u p + v) / (p + w) through three points (p3 < 0: p3 = inf)."""
     if p3 > 0.0:

@@ -89,6 +89,61 @@ extern "C" void hostcheck_dd(int op, const double* a, const double* b, double* o
   out[0] = r.hi; out[1] = r.lo;
 }
 
+// ---- the partition of the band solvers (spline_fit.hip.h: BandParts, band_parts, band_parts_fixed) ----
+// P == 0: the production rule with `min_rows`; P >= 2: band_parts_fixed.  out = P, len, rem; returns 0 for an explicit P that is not legal
+extern "C" int hostcheck_band_parts(int n, int HB, int P, int min_rows, int* out) {
+  if (P != 0 && !band_parts_legal(n, HB, P)) return 0;
+  const BandParts bp = P == 0 ? band_parts(n, HB, min_rows) : band_parts_fixed(n, HB, P);
+  out[0] = bp.P; out[1] = bp.len; out[2] = bp.rem;
+  return 1;
+}
+static BandParts band_parts_of(int HB, int P, int len, int rem) { BandParts bp; bp.HB = HB; bp.P = P; bp.len = len; bp.rem = rem; return bp; }
+// first[P], length[P] and locate() of rows 0..n-1 of a partition
+extern "C" void hostcheck_band_layout(int n, int HB, int P, int len, int rem, int* first, int* length, int* loc_p, int* loc_i) {
+  const BandParts bp = band_parts_of(HB, P, len, rem);
+  for (int p = 0; p < P; ++p) { first[p] = bp.first(p); length[p] = bp.length(p); }
+  for (int j = 0; j < n; ++j) bp.locate(j, loc_p[j], loc_i[j]);
+}
+// at(p, i, k, K) for count index triples
+extern "C" void hostcheck_band_at(int HB, int P, int len, int rem, int K, long long count, const int* p, const int* i, const int* k, long long* at) {
+  const BandParts bp = band_parts_of(HB, P, len, rem);
+  for (long long e = 0; e < count; ++e) at[e] = bp.at(p[e], i[e], k[e], K);
+}
+// Every legal explicit P of (n, HB), and the production rule (min_rows): violations counted per invariant, all 0 for a sound partition.
+//   counts[0] partitions looked at; [1] rows whose locate() is not the walk interior 0, separator 0, interior 1, .. in order, or whose
+//   first() / length() disagree with it; [2] partitions that do not end at row n; [3] interiors shorter than 2 HB;
+//   [4] at() past K * rows for the K of an array (rows = n + kBandPartsMax; K = HB + 1, 3, HB); [5] with walk_at != 0: at() values that are
+//   not the running count over (i, k, p), i.e. not injective
+extern "C" void hostcheck_band_parts_sweep(int n, int HB, int min_rows, int walk_at, long long* counts) {
+  for (int k = 0; k < 6; ++k) counts[k] = 0;
+  const long long rows = (long long)n + kBandPartsMax;
+  for (int P = 1; P <= kBandPartsMax; ++P) {
+    BandParts bp;
+    if (P == 1) { bp = band_parts(n, HB, min_rows); if (bp.P < 2) continue; }       // (P == 1 stands for the rule)
+    else if (band_parts_legal(n, HB, P)) bp = band_parts_fixed(n, HB, P);
+    else continue;
+    ++counts[0];
+    int p = 0, i = 0, lmax = 0;
+    for (int j = 0; j < n; ++j) {
+      int lp, li;
+      bp.locate(j, lp, li);
+      if (lp != p || li != i || bp.first(p) + i != j) ++counts[1];
+      ++i;
+      if (p + 1 < bp.P && i == bp.length(p) + HB) { ++p; i = 0; }
+    }
+    if (p != bp.P - 1 || i != bp.length(bp.P - 1)) ++counts[2];
+    for (int q = 0; q < bp.P; ++q) { if (bp.length(q) < 2 * HB) ++counts[3]; lmax = std::max(lmax, bp.length(q)); }
+    const int Ks[3] = {HB + 1, 3, HB};
+    for (int K : Ks) {
+      for (int q = 0; q < bp.P; ++q) if (bp.at(q, bp.length(q) - 1, K - 1, K) >= K * rows) ++counts[4];
+      if (walk_at) {
+        long long run = 0;
+        for (int ii = 0; ii < lmax; ++ii) for (int k = 0; k < K; ++k) for (int q = 0; q < bp.P; ++q, ++run) if (bp.at(q, ii, k, K) != run) ++counts[5];
+      }
+    }
+  }
+}
+
 // host build of the PnP math (mvus_amd/csrc/pnp.hip.h)
 extern "C" int hostcheck_pnp_dlt6(const double* Xs /* [6][3] */, const double* xn /* [6][2] */, double* R, double* t) {
   return pnp_dlt6(reinterpret_cast<const double (*)[3]>(Xs), reinterpret_cast<const double (*)[2]>(xn), R, t) ? 1 : 0;
