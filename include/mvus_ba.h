@@ -522,6 +522,30 @@ int mvus_spline_band_solve(int32_t device, int32_t n, int32_t hb, int32_t precis
  * pass.  Arguments as above.  MVUS_E_INVALID: n < 4, G5 or out NULL. */
 int mvus_spline_band_diag_sum(int32_t device, int32_t n, int32_t precise, const double* G5, const double* G5_lo, double* out);
 
+/* The passes of that fit before and after its banded solve, on samples, knots and coefficients handed in: inspection hooks for k_fit_basis,
+ * k_fit_first, k_fit_blocks, k_fit_slice_sum, k_fit_band, k_fit_penalty, k_fit_residual, k_fit_total_partial / k_fit_total and k_fit_fpint /
+ * k_fit_fpint_final (spline_fit.hip.h), with the fit's own launches and work-array sizes for exactly these n knots.  No reference
+ * counterpart.  u[m], X[3*m] as in mvus_spline_smooth; t[n] a cubic knot vector on them; ncoef = n - 4 coefficients, nspan = n - 7 spans.
+ *   slices == 0: a span's samples are cut into the fit's own number of slices (fit_slices(nspan)); slices >= 1: exactly that many.
+ *   precise, parts, the _lo words, stats_out[4] and *fail_out: as in mvus_spline_band_solve (hb = 3).
+ * mvus_spline_fit_normal, one least-squares pass: span_out[m] (the span of every sample, 0-based), q_out[4*m] (its four B-splines),
+ *   first_out[nspan + 1] (the first sample of every span, first[nspan] = m), G5_out / G5_lo_out[5*ncoef] and rhs_out / rhs_lo_out[3*ncoef]
+ *   (the normal equations as the solver reads them; the _lo outputs may be NULL), c_out[3*ncoef] (their solution).
+ * mvus_spline_fit_penalty: BtB_out / BtB_lo_out[5*ncoef] = B^T B of the n8 x ncoef jump matrix b[5*n8] (fpdisc's layout: row it holds
+ *   columns it .. it + 4), by k_fit_penalty alone.
+ * mvus_spline_fit_residual: term_out[m] = |s(u_i) - X_i|^2 for the coefficients c[3*ncoef], *fp_out their total, fpint_out[nspan] the
+ *   per-span sums with FITPACK's half / half rule for the sample that opens a span.
+ * MVUS_E_INVALID, before any launch: a NULL pointer other than the _lo ones; m <= 3; u not strictly increasing; a non-finite input;
+ * n < 8 or n > m + 4; boundary knots other than u[0] / u[m-1] four times each; interior knots not strictly increasing inside
+ * (u[0], u[m-1]); a span without a sample; slices < 0, > 256, nspan (slices - 1) > 1536 or nspan slices > 2048 (what the fit's slice
+ * arrays hold); parts as in mvus_spline_band_solve; for the penalty, n8 < 1 or n8 > ncoef - 4.  Stateless; no CPU fallback. */
+int mvus_spline_fit_normal(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, int32_t precise, int32_t slices,
+                           int32_t parts, int32_t* span_out, double* q_out, int64_t* first_out, double* G5_out, double* G5_lo_out, double* rhs_out,
+                           double* rhs_lo_out, double* c_out, double* stats_out, int32_t* fail_out);
+int mvus_spline_fit_penalty(int32_t device, int32_t ncoef, int32_t n8, const double* b, int32_t precise, double* BtB_out, double* BtB_lo_out);
+int mvus_spline_fit_residual(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, const double* c, int32_t slices,
+                             double* term_out, double* fp_out, double* fpint_out);
+
 /* Scene.get_camera_pose's cv2.solvePnPRansac(objectPoints, imagePoints, K, d, reprojectionError=error) (common.py:744; OpenCV is
  * a third-party dependency absent from this image: parity unpinned, see pnp.hip.h).  X[3*N] object points (x(N) y(N) z(N)),
  * uv[2*N] raw pixels (u(N) v(N)), K = fx fy cx cy, d = k1 k2 p1 p2 k3.  `iterations` hypotheses (OpenCV's iterationsCount,

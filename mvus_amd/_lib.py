@@ -122,6 +122,11 @@ API = [
     ('mvus_spline_fit_close', None, [ctypes.c_void_p]),
     ('mvus_spline_band_solve', ctypes.c_int, [ctypes.c_int32] * 5 + [c_double_p] * 4 + [ctypes.c_double] + [c_double_p] * 4 + [c_int32_p, c_int32_p]),
     ('mvus_spline_band_diag_sum', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
+    ('mvus_spline_fit_normal', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int32, c_double_p] + [ctypes.c_int32] * 3
+                                             + [c_int32_p, c_double_p, c_int64_p] + [c_double_p] * 6 + [c_int32_p]),
+    ('mvus_spline_fit_penalty', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_double_p, ctypes.c_int32, c_double_p, c_double_p]),
+    ('mvus_spline_fit_residual', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_int32,
+                                               c_double_p, c_double_p, c_double_p]),
     ('mvus_pnp_ransac', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_int32,
                                        ctypes.c_uint64, c_double_p, c_double_p, c_uint8_p, c_int64_p]),
     ('mvus_triangulate', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),

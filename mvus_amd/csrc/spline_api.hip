@@ -49,16 +49,33 @@ static bool fit_band_solve(hipStream_t st, FitWork<T>& w, int ncoef, const T* Mb
   return fit_band_solve<HB, T>(st, w, ncoef, band_parts(ncoef, HB, band_parts_min()), Mband, cd, out, fail);
 }
 // least-squares spline on the current knots: normal equations from the span blocks, banded Cholesky, coefficients -> cd
+// (nslice slices per span -- the fit passes fit_slices(nrint) -- and the partition bp of the solve: band_parts(ncoef, 3, band_parts_min()))
 template <class T>
 static bool fit_lsq_pass(hipStream_t st, FitWork<T>& w, long long m, const long long* first, const double* q, const double* dX, int ncoef, int nrint,
-                         double* cd, double* out, int* fail) {
+                         int nslice, const BandParts& bp, double* cd, double* out, int* fail) {
   constexpr int NT = sizeof(T) == sizeof(double) ? 256 : 64;
-  const int nslice = fit_slices(nrint);
   hipLaunchKernelGGL((k_fit_blocks<T, NT>), dim3(nrint, nslice), dim3(NT), 0, st, m, first, q, dX, w.SB);
   if (nslice > 1) hipLaunchKernelGGL(k_fit_slice_sum<T>, fit_blocks((long long)nrint * kFitBlk), dim3(256), 0, st, (long long)nrint * kFitBlk, nslice, w.SB);
-  hipLaunchKernelGGL(k_fit_band<T>, fit_blocks(ncoef), dim3(256), 0, st, ncoef, nrint, w.SB, w.G5, w.rhs, band_parts(ncoef, 3, band_parts_min()), w.Lf, w.yw);
+  hipLaunchKernelGGL(k_fit_band<T>, fit_blocks(ncoef), dim3(256), 0, st, ncoef, nrint, w.SB, w.G5, w.rhs, bp, w.Lf, w.yw);
   w.penalty = false;
-  return fit_band_solve<3, T>(st, w, ncoef, w.G5, cd, out, fail);
+  return fit_band_solve<3, T>(st, w, ncoef, bp, w.G5, cd, out, fail);
+}
+// c -> the squared residual of every sample (term), their total f_p (out[1]) and, with `spans`, the per-span sums (out[4 + sp]) in
+// nslice slices per span (the fit passes fit_slices(nspan))
+static void fit_residual_pass(hipStream_t st, long long m, int ncoef, const int32_t* span, const double* q, const double* dX, const double* cd, double* term,
+                              double* tot_part, double* out, bool spans, int nspan, int nslice, const long long* first, double* fp_part) {
+  hipLaunchKernelGGL(k_fit_residual, fit_blocks(m), dim3(256), 0, st, m, ncoef, span, q, dX, cd, term);
+  if (m > kFitTotalOneStage) {                                    // two stages (still one fixed order)
+    const int nbt = fit_total_parts(m);
+    hipLaunchKernelGGL(k_fit_total_partial, dim3(nbt), dim3(256), 0, st, m, term, tot_part);
+    hipLaunchKernelGGL(k_fit_total, dim3(1), dim3(256), 0, st, (long long)nbt, tot_part, out + 1);
+  } else {
+    hipLaunchKernelGGL(k_fit_total, dim3(1), dim3(256), 0, st, m, term, out + 1);
+  }
+  if (spans) {
+    hipLaunchKernelGGL(k_fit_fpint, dim3(nspan, nslice), dim3(256), 0, st, nspan, first, term, out + 4, fp_part);
+    if (nslice > 1) hipLaunchKernelGGL(k_fit_fpint_final, fit_blocks(nspan), dim3(256), 0, st, nspan, nslice, first, term, fp_part, out + 4);
+  }
 }
 // the sum of the factor's diagonal in the natural elimination order (fppara's initial p) when the last pass was partitioned
 template <class T>
@@ -132,6 +149,89 @@ static int band_diag_sum_run(int32_t device, int n, const double* G5, const doub
   MVUS_HIP(hipGetLastError());
   MVUS_HIP(hipMemcpyAsync(out_host, out, sizeof(double), hipMemcpyDeviceToHost, cb.st));
   MVUS_HIP(hipStreamSynchronize(cb.st));
+  return MVUS_OK;
+}
+
+// ---- inspection: the passes of the fit around those solvers (mvus_spline_fit_normal, _penalty, _residual) ----------------------------------
+// `count` values of a work array back on the host as high and low words (lo may be NULL; 0 in fp64)
+static void band_read(CallBuffers& cb, const double* src, double* hi, double* lo, size_t count) {
+  MVUS_HIP(hipMemcpyAsync(hi, src, sizeof(double) * count, hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipStreamSynchronize(cb.st));
+  if (lo) std::fill(lo, lo + count, 0.0);
+}
+static void band_read(CallBuffers& cb, const dd* src, double* hi, double* lo, size_t count) {
+  std::vector<dd> stage(count);
+  MVUS_HIP(hipMemcpyAsync(stage.data(), src, sizeof(dd) * count, hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipStreamSynchronize(cb.st));
+  for (size_t i = 0; i < count; ++i) { hi[i] = stage[i].hi; if (lo) lo[i] = stage[i].lo; }
+}
+// the checks the three share; slices: 0 the production rule, else exactly that many
+static bool fit_inspect_args_ok(const char* name, int64_t m, const double* u, const double* X, int32_t n, const double* t, int32_t slices) {
+  if (const char* wrong = fit_samples_knots_wrong(m, u, n, t)) { g_create_error = std::string(name) + ": " + wrong; return false; }
+  for (int64_t i = 0; i < 3 * m; ++i) if (!std::isfinite(X[i])) { g_create_error = std::string(name) + ": non-finite sample"; return false; }
+  if (slices != 0 && !fit_slices_legal(n - 7, slices)) {
+    g_create_error = std::string(name) + ": slices must be 0 (the production rule) or 1..256 with spans x (slices - 1) <= 1536 and spans x slices <= 2048";
+    return false;
+  }
+  return true;
+}
+// samples and knots on the device, then what every pass of the fit starts with: k_fit_basis and k_fit_first
+struct FitInputs {
+  const double *du = nullptr, *dX = nullptr, *td = nullptr;
+  int32_t* span = nullptr;
+  double* q = nullptr;
+  long long* first = nullptr;
+  void upload(CallBuffers& cb, int64_t m, const double* u, const double* X, int n, const double* t) {
+    const int ncoef = n - 4, nspan = n - 7;
+    du = cb.put(u, (size_t)m); dX = cb.put(X, 3 * (size_t)m); td = cb.put(t, (size_t)n);
+    span = cb.get<int32_t>((size_t)m); q = cb.get<double>(4 * (size_t)m); first = cb.get<long long>((size_t)nspan + 1);
+    hipLaunchKernelGGL(k_fit_basis, fit_blocks(m), dim3(256), 0, cb.st, (long long)m, du, td, ncoef, span, q);
+    hipLaunchKernelGGL(k_fit_first, fit_blocks(nspan + 1), dim3(256), 0, cb.st, (long long)m, du, td, nspan, first);
+  }
+};
+template <class T>
+static int fit_normal_run(int32_t device, int64_t m, const double* u, const double* X, int n, const double* t, int slices, const BandParts& bp, int32_t* span_out,
+                          double* q_out, int64_t* first_out, double* G5_out, double* G5_lo_out, double* rhs_out, double* rhs_lo_out, double* c_out,
+                          double* stats_out, int32_t* fail_out) {
+  const int ncoef = n - 4, nspan = n - 7;
+  CallBuffers cb;
+  cb.open(device);
+  FitInputs in;
+  in.upload(cb, m, u, X, n, t);
+  FitWork<T> w;
+  w.alloc(cb, (size_t)n);
+  double* cd = cb.get<double>(3 * (size_t)ncoef);
+  double* out = cb.get<double>(4);
+  int* fail = cb.get<int>(1);
+  const double unset = std::nan("");
+  const double out0[4] = {unset, unset, unset, unset};
+  MVUS_HIP(hipMemcpyAsync(out, out0, sizeof(out0), hipMemcpyHostToDevice, cb.st));
+  MVUS_HIP(hipMemsetAsync(fail, 0, sizeof(int), cb.st));
+  fit_lsq_pass<T>(cb.st, w, (long long)m, in.first, in.q, in.dX, ncoef, nspan, slices ? slices : fit_slices(nspan), bp, cd, out, fail);
+  MVUS_HIP(hipGetLastError());
+  int fh = 0;
+  std::vector<long long> fh_first((size_t)nspan + 1);
+  MVUS_HIP(hipMemcpyAsync(span_out, in.span, sizeof(int32_t) * m, hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipMemcpyAsync(q_out, in.q, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipMemcpyAsync(fh_first.data(), in.first, sizeof(long long) * (nspan + 1), hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipMemcpyAsync(c_out, cd, sizeof(double) * 3 * ncoef, hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipMemcpyAsync(stats_out, out, sizeof(double) * 4, hipMemcpyDeviceToHost, cb.st));
+  MVUS_HIP(hipMemcpyAsync(&fh, fail, sizeof(int), hipMemcpyDeviceToHost, cb.st));
+  band_read(cb, w.G5, G5_out, G5_lo_out, 5 * (size_t)ncoef);
+  band_read(cb, w.rhs, rhs_out, rhs_lo_out, 3 * (size_t)ncoef);
+  for (int sp = 0; sp <= nspan; ++sp) first_out[sp] = fh_first[sp];
+  *fail_out = fh;
+  return MVUS_OK;
+}
+template <class T>
+static int fit_penalty_run(int32_t device, int ncoef, int n8, const double* b, double* BtB_out, double* BtB_lo_out) {
+  CallBuffers cb;
+  cb.open(device);
+  const double* bd = cb.put(b, 5 * (size_t)n8);
+  T* BtB = cb.get<T>(5 * (size_t)ncoef);
+  hipLaunchKernelGGL(k_fit_penalty<T>, fit_blocks(ncoef), dim3(256), 0, cb.st, ncoef, n8, bd, BtB);
+  MVUS_HIP(hipGetLastError());
+  band_read(cb, BtB, BtB_out, BtB_lo_out, 5 * (size_t)ncoef);
   return MVUS_OK;
 }
 
@@ -362,7 +462,7 @@ static int spline_fit_open_impl(mvus_spline_fit& S, int32_t device, int64_t m, c
     S.span = cb.get<int32_t>((size_t)m);
     S.q = cb.get<double>(4 * (size_t)m);
     S.term = cb.get<double>((size_t)m);
-    S.tot_part = cb.get<double>(1024);
+    S.tot_part = cb.get<double>(kFitTotalParts);
     S.fp_part = cb.get<double>(512 + kFitSliceBlocks);
     S.fail = cb.get<int>(1);
     MVUS_HIP(hipStreamSynchronize(cb.st));                 // u and X may go away after this call
@@ -430,19 +530,7 @@ static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* 
     nrdata[0] = (int)m - 2;
     auto blocks = fit_blocks;
     auto residual = [&](int ncoef, bool spans, int nspan) {            // c -> f_p (and the per-span residuals), fetched
-      hipLaunchKernelGGL(k_fit_residual, blocks(m), dim3(256), 0, cb.st, (long long)m, ncoef, span, q, dX, cd, term);
-      if (m > 8192) {                                                 // two stages (still one fixed order)
-        const int nbt = (int)std::min<long long>(1024, (m + 2047) / 2048);
-        hipLaunchKernelGGL(k_fit_total_partial, dim3(nbt), dim3(256), 0, cb.st, (long long)m, term, tot_part);
-        hipLaunchKernelGGL(k_fit_total, dim3(1), dim3(256), 0, cb.st, (long long)nbt, tot_part, out + 1);
-      } else {
-        hipLaunchKernelGGL(k_fit_total, dim3(1), dim3(256), 0, cb.st, (long long)m, term, out + 1);
-      }
-      if (spans) {
-        const int nslice = fit_slices(nspan);
-        hipLaunchKernelGGL(k_fit_fpint, dim3(nspan, nslice), dim3(256), 0, cb.st, nspan, first, term, out + 4, fp_part);
-        if (nslice > 1) hipLaunchKernelGGL(k_fit_fpint_final, blocks(nspan), dim3(256), 0, cb.st, nspan, nslice, first, term, fp_part, out + 4);
-      }
+      fit_residual_pass(cb.st, (long long)m, ncoef, span, q, dX, cd, term, tot_part, out, spans, nspan, fit_slices(nspan), first, fp_part);
       MVUS_HIP(hipGetLastError());
       MVUS_HIP(hipMemcpyAsync(host.data(), out, sizeof(double) * (4 + (spans ? nspan : 0)), hipMemcpyDeviceToHost, cb.st));
       MVUS_HIP(hipMemcpyAsync(&failed, fail, sizeof(int), hipMemcpyDeviceToHost, cb.st));
@@ -454,11 +542,14 @@ static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* 
     auto solve = [&](int ncoef, int nrint_, int n8, bool smoothing, double pinv) {
       for (int attempt = 0; attempt < 2; ++attempt) {
         if (!precise) {
-          if (!smoothing) diag_natural = fit_lsq_pass<double>(cb.st, w1, (long long)m, first, q, dX, ncoef, nrint_, cd, out, fail);
+          if (!smoothing) diag_natural = fit_lsq_pass<double>(cb.st, w1, (long long)m, first, q, dX, ncoef, nrint_, fit_slices(nrint_), band_parts(ncoef, 3, band_parts_min()), cd, out, fail);
           else fit_smooth_pass<double>(cb.st, w1, ncoef, n8, bd, pinv, cd, out, fail);
         } else {
           w2.alloc(cb, cap);
-          if (lsq_dd_n != n) { diag_natural = fit_lsq_pass<dd>(cb.st, w2, (long long)m, first, q, dX, ncoef, nrint_, cd, out, fail); lsq_dd_n = n; }
+          if (lsq_dd_n != n) {
+            diag_natural = fit_lsq_pass<dd>(cb.st, w2, (long long)m, first, q, dX, ncoef, nrint_, fit_slices(nrint_), band_parts(ncoef, 3, band_parts_min()), cd, out, fail);
+            lsq_dd_n = n;
+          }
           if (smoothing) fit_smooth_pass<dd>(cb.st, w2, ncoef, n8, bd, pinv, cd, out, fail);
         }
         residual(ncoef, !smoothing, nrint_);
@@ -629,6 +720,57 @@ int mvus_spline_band_solve(int32_t device, int32_t n, int32_t hb, int32_t precis
 int mvus_spline_band_diag_sum(int32_t device, int32_t n, int32_t precise, const double* G5, const double* G5_lo, double* out) {
   if (n < 4 || !G5 || !out) { g_create_error = "spline_band_diag_sum: bad arguments (n >= 4)"; return MVUS_E_INVALID; }
   return stateless([&] { return precise ? band_diag_sum_run<dd>(device, n, G5, G5_lo, out) : band_diag_sum_run<double>(device, n, G5, G5_lo, out); });
+}
+
+int mvus_spline_fit_normal(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, int32_t precise, int32_t slices,
+                           int32_t parts, int32_t* span_out, double* q_out, int64_t* first_out, double* G5_out, double* G5_lo_out, double* rhs_out,
+                           double* rhs_lo_out, double* c_out, double* stats_out, int32_t* fail_out) {
+  if (!X || !span_out || !q_out || !first_out || !G5_out || !rhs_out || !c_out || !stats_out || !fail_out) { g_create_error = "spline_fit_normal: bad arguments"; return MVUS_E_INVALID; }
+  if (!fit_inspect_args_ok("spline_fit_normal", m, u, X, n, t, slices)) return MVUS_E_INVALID;
+  const int ncoef = n - 4;
+  if (parts < -1 || parts == 1 || (parts >= 2 && !band_parts_legal(ncoef, 3, parts))) {
+    g_create_error = "spline_fit_normal: parts must be -1 (one chain), 0 (the production rule) or 2..256 interiors of at least 6 rows";
+    return MVUS_E_INVALID;
+  }
+  BandParts bp;
+  if (parts == 0) bp = band_parts(ncoef, 3, 192);
+  else if (parts >= 2) bp = band_parts_fixed(ncoef, 3, parts);
+  return stateless([&] {
+    return precise ? fit_normal_run<dd>(device, m, u, X, n, t, slices, bp, span_out, q_out, first_out, G5_out, G5_lo_out, rhs_out, rhs_lo_out, c_out, stats_out, fail_out)
+                   : fit_normal_run<double>(device, m, u, X, n, t, slices, bp, span_out, q_out, first_out, G5_out, G5_lo_out, rhs_out, rhs_lo_out, c_out, stats_out, fail_out);
+  });
+}
+
+int mvus_spline_fit_penalty(int32_t device, int32_t ncoef, int32_t n8, const double* b, int32_t precise, double* BtB_out, double* BtB_lo_out) {
+  if (ncoef < 5 || n8 < 1 || n8 > ncoef - 4 || !b || !BtB_out) { g_create_error = "spline_fit_penalty: bad arguments (1 <= n8 <= ncoef - 4 rows of b)"; return MVUS_E_INVALID; }
+  for (int64_t i = 0; i < 5ll * n8; ++i) if (!std::isfinite(b[i])) { g_create_error = "spline_fit_penalty: non-finite b"; return MVUS_E_INVALID; }
+  return stateless([&] { return precise ? fit_penalty_run<dd>(device, ncoef, n8, b, BtB_out, BtB_lo_out) : fit_penalty_run<double>(device, ncoef, n8, b, BtB_out, BtB_lo_out); });
+}
+
+int mvus_spline_fit_residual(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, const double* c, int32_t slices,
+                             double* term_out, double* fp_out, double* fpint_out) {
+  if (!X || !c || !term_out || !fp_out || !fpint_out) { g_create_error = "spline_fit_residual: bad arguments"; return MVUS_E_INVALID; }
+  if (!fit_inspect_args_ok("spline_fit_residual", m, u, X, n, t, slices)) return MVUS_E_INVALID;
+  const int ncoef = n - 4, nspan = n - 7;
+  for (int i = 0; i < 3 * ncoef; ++i) if (!std::isfinite(c[i])) { g_create_error = "spline_fit_residual: non-finite coefficient"; return MVUS_E_INVALID; }
+  return stateless([&] {
+    CallBuffers cb;
+    cb.open(device);
+    FitInputs in;
+    in.upload(cb, m, u, X, n, t);
+    const double* cd = cb.put(c, 3 * (size_t)ncoef);
+    double* term = cb.get<double>((size_t)m);
+    double* tot_part = cb.get<double>(kFitTotalParts);
+    double* fp_part = cb.get<double>(512 + kFitSliceBlocks);
+    double* out = cb.get<double>((size_t)n + 4);
+    fit_residual_pass(cb.st, (long long)m, ncoef, in.span, in.q, in.dX, cd, term, tot_part, out, true, nspan, slices ? slices : fit_slices(nspan), in.first, fp_part);
+    MVUS_HIP(hipGetLastError());
+    MVUS_HIP(hipMemcpyAsync(term_out, term, sizeof(double) * m, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipMemcpyAsync(fp_out, out + 1, sizeof(double), hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipMemcpyAsync(fpint_out, out + 4, sizeof(double) * nspan, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipStreamSynchronize(cb.st));
+    return MVUS_OK;
+  });
 }
 
 }  // extern "C"

@@ -115,9 +115,43 @@ inline BandParts band_parts(int n, int HB, int min_rows) {
   if (P < 2) return bp;
   return band_parts_fixed(n, HB, P);
 }
-#if defined(__HIPCC__)
 constexpr int kFitBlk = 22;      // per span: 10 products h_a h_b (a >= b) + 12 products h_a x_d
-
+// A span with many samples (the first passes of a fit: ONE span holds all 3.3 M samples of a long trajectory) is cut into
+// gridDim.y slices, one workgroup each; slice `sl` of span `sp` goes to block sl * nspan + sp of SB and k_fit_slice_sum adds the
+// slices in their order.  fit_slices() picks the count from the number of spans alone, so the order of every sum is fixed.
+inline int fit_slices(int nspan) {
+  static const int cap = [] { const char* e = std::getenv("MVUS_FIT_SLICES_MAX"); return e ? std::max(1, std::min(256, std::atoi(e))) : 256; }();
+  return nspan >= 512 ? 1 : std::min(cap, (1024 + nspan - 1) / nspan);
+}
+constexpr int kFitSliceBlocks = 1536;              // nspan * fit_slices(nspan) - nspan stays below this
+// the total f_p of m > kFitTotalOneStage samples takes two stages: this many workgroups of k_fit_total_partial, then k_fit_total
+constexpr long long kFitTotalOneStage = 8192;
+constexpr int kFitTotalParts = 1024;               // the size of tot_part
+inline int fit_total_parts(long long m) { return (int)std::min<long long>(kFitTotalParts, (m + 2047) / 2048); }
+// an explicit slice count (the inspection entry points): the blocks of SB and the partial sums of fp_part it writes fit what the fit allocates
+inline bool fit_slices_legal(int nspan, int slices) {
+  return slices >= 1 && slices <= 256 && (long long)nspan * (slices - 1) <= kFitSliceBlocks && (slices == 1 || (long long)nspan * slices <= 512 + kFitSliceBlocks);
+}
+// What the inspection entry points of the fit's passes accept as samples and knots: m > 3 strictly increasing finite u, n >= 8 knots with
+// u[0] / u[m-1] four times at the ends, interior knots strictly increasing inside (u[0], u[m-1]), and no span without a sample (fppara
+// cannot produce one -- every interior knot it places is a sample and opens its span -- so the half / half rule has no contract there).
+// Returns NULL, or what is wrong.
+inline const char* fit_samples_knots_wrong(long long m, const double* u, int n, const double* t) {
+  if (m <= 3 || m > (1ll << 30) || !u || !t) return "m > 3 samples and a knot vector";
+  if (n < 8 || n > m + 4) return "8 <= n <= m + 4 knots";
+  for (long long i = 0; i < m; ++i) if (!std::isfinite(u[i])) return "non-finite timestamp";
+  for (long long i = 1; i < m; ++i) if (!(u[i] > u[i - 1])) return "the timestamps must be strictly increasing";
+  for (int j = 0; j < n; ++j) if (!std::isfinite(t[j])) return "non-finite knot";
+  for (int j = 0; j < 4; ++j) if (t[j] != u[0] || t[n - 1 - j] != u[m - 1]) return "the boundary knots must be u[0] and u[m-1], four times each";
+  for (int j = 4; j <= n - 4; ++j) if (!(t[j] > t[j - 1])) return "the interior knots must be strictly increasing inside (u[0], u[m-1])";
+  long long i = 0;                                   // every span [t[3 + sp], t[4 + sp]) holds a sample (the last one: its right end too)
+  for (int sp = 0; sp + 8 <= n; ++sp) {
+    while (i < m && u[i] < t[3 + sp]) ++i;
+    if (i >= m || (sp + 8 < n && !(u[i] < t[4 + sp]))) return "a span without a sample";
+  }
+  return nullptr;
+}
+#if defined(__HIPCC__)
 
 __global__ __launch_bounds__(256) void k_fit_basis(long long m, const double* __restrict__ u, const double* __restrict__ t, int ncoef,
                                                    int32_t* __restrict__ span, double* __restrict__ q) {
@@ -164,14 +198,7 @@ __device__ __forceinline__ void block_sum(T (&v)[NV], T* lds) {
   for (int k = 0; k < NV; ++k) v[k] = lds[k * NT];
 }
 
-// A span with many samples (the first passes of a fit: ONE span holds all 3.3 M samples of a long trajectory) is cut into
-// gridDim.y slices, one workgroup each; slice `sl` of span `sp` goes to block sl * nspan + sp of SB and k_fit_slice_sum adds the
-// slices in their order.  fit_slices() picks the count from the number of spans alone, so the order of every sum is fixed.
-inline int fit_slices(int nspan) {
-  static const int cap = [] { const char* e = std::getenv("MVUS_FIT_SLICES_MAX"); return e ? std::max(1, std::min(256, std::atoi(e))) : 256; }();
-  return nspan >= 512 ? 1 : std::min(cap, (1024 + nspan - 1) / nspan);
-}
-constexpr int kFitSliceBlocks = 1536;              // nspan * fit_slices(nspan) - nspan stays below this
+// one workgroup per (span, slice): see fit_slices above
 template <class T, int NT>
 __global__ __launch_bounds__(NT) void k_fit_blocks(long long m, const long long* __restrict__ first, const double* __restrict__ q,
                                                    const double* __restrict__ X, T* __restrict__ SB) {

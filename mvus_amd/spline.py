@@ -278,6 +278,70 @@ def band_diag_sum(G5, precise=False, G5_lo=None, device=0):
     return float(out[0])
 
 
+def _fit_samples(u, X, t):
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    if u.ndim != 1 or t.ndim != 1 or X.shape != (3, u.size):
+        raise ValueError('u[m], X[3, m] and a 1-D knot vector expected')
+    return u, X, t
+
+
+def fit_normal(u, X, t, precise=False, slices=0, parts=0, device=0):
+    """One least-squares pass of the smoothing fit on the knots ``t`` (``mvus_spline_fit_normal``, an inspection hook): k_fit_basis,
+    k_fit_first, then the fit's own assembly and banded solve, in fp64 or (``precise``) double-double.  ``slices`` = 0: the fit's
+    rule, >= 1: that many slices per span; ``parts`` as in ``band_solve``.  Returns a namespace: span[m], q[m, 4], first[nspan + 1],
+    G5 / G5_lo[ncoef, 5], rhs / rhs_lo[3, ncoef], c[3, ncoef], stats[4], fail."""
+    from types import SimpleNamespace
+    lib = _lib.load()
+    u, X, t = _fit_samples(u, X, t)
+    m, n = u.size, t.size
+    nc, ns = max(n - 4, 1), max(n - 7, 1)
+    span, q, first = np.zeros(m, np.int32), np.zeros((m, 4)), np.zeros(ns + 1, np.int64)
+    G5, G5_lo, rhs, rhs_lo, c, stats = np.zeros((nc, 5)), np.zeros((nc, 5)), np.zeros((3, nc)), np.zeros((3, nc)), np.zeros((3, nc)), np.zeros(4)
+    fail = ctypes.c_int32(0)
+    rc = lib.mvus_spline_fit_normal(int(device), m, _lib.dptr(u), _lib.dptr(X), n, _lib.dptr(t), int(bool(precise)), int(slices), int(parts),
+                                    span.ctypes.data_as(_lib.c_int32_p), _lib.dptr(q), first.ctypes.data_as(_lib.c_int64_p), _lib.dptr(G5), _lib.dptr(G5_lo),
+                                    _lib.dptr(rhs), _lib.dptr(rhs_lo), _lib.dptr(c), _lib.dptr(stats), ctypes.byref(fail))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_fit_normal')
+    return SimpleNamespace(span=span, q=q, first=first, G5=G5, G5_lo=G5_lo, rhs=rhs, rhs_lo=rhs_lo, c=c, stats=stats, fail=fail.value)
+
+
+def fit_penalty(b, ncoef, precise=False, device=0):
+    """B^T B of the jump matrix ``b[n8, 5]`` (fpdisc's layout) over ``ncoef`` coefficients by k_fit_penalty alone
+    (``mvus_spline_fit_penalty``, an inspection hook).  Returns (BtB[ncoef, 5], BtB_lo[ncoef, 5]) in ``band_solve``'s layout."""
+    lib = _lib.load()
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] != 5:
+        raise ValueError('b[n8, 5] expected')
+    nc = max(int(ncoef), 1)
+    BtB, BtB_lo = np.zeros((nc, 5)), np.zeros((nc, 5))
+    rc = lib.mvus_spline_fit_penalty(int(device), int(ncoef), b.shape[0], _lib.dptr(b), int(bool(precise)), _lib.dptr(BtB), _lib.dptr(BtB_lo))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_fit_penalty')
+    return BtB, BtB_lo
+
+
+def fit_residual(u, X, t, c, slices=0, device=0):
+    """The residual pass of the smoothing fit for coefficients ``c[3, ncoef]`` on the knots ``t`` (``mvus_spline_fit_residual``, an
+    inspection hook): returns a namespace with term[m] (squared residual per sample), fp (their total) and fpint[nspan] (per span,
+    the sample that opens a span shared half / half with the span before)."""
+    from types import SimpleNamespace
+    lib = _lib.load()
+    u, X, t = _fit_samples(u, X, t)
+    m, n = u.size, t.size
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if c.shape != (3, n - 4):
+        raise ValueError('c has shape %s, expected (3, %d)' % (c.shape, n - 4))
+    term, fp, fpint = np.zeros(m), np.zeros(1), np.zeros(max(n - 7, 1))
+    rc = lib.mvus_spline_fit_residual(int(device), m, _lib.dptr(u), _lib.dptr(X), n, _lib.dptr(t), _lib.dptr(c), int(slices), _lib.dptr(term), _lib.dptr(fp),
+                                      _lib.dptr(fpint))
+    if rc != 0:
+        _err(lib, rc, 'mvus_spline_fit_residual')
+    return SimpleNamespace(term=term, fp=float(fp[0]), fpint=fpint)
+
+
 def _fprati(p1, f1, p2, f2, p3, f3):
     """FITPACK fprati: the zero of the rational interpolant r(p) = (u p + v) / (p + w) through three points (p3 < 0: p3 = inf)."""
     if p3 > 0.0:

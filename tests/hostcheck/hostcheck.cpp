@@ -144,6 +144,15 @@ extern "C" void hostcheck_band_parts_sweep(int n, int HB, int min_rows, int walk
   }
 }
 
+// ---- the sizes of the fit's sliced passes and of its two-stage total (spline_fit.hip.h) ----
+// out = kFitBlk, kFitSliceBlocks, kFitTotalOneStage, kFitTotalParts
+extern "C" void hostcheck_fit_constants(long long* out) { out[0] = kFitBlk; out[1] = kFitSliceBlocks; out[2] = kFitTotalOneStage; out[3] = kFitTotalParts; }
+extern "C" int hostcheck_fit_slices(int nspan) { return fit_slices(nspan); }
+extern "C" int hostcheck_fit_slices_legal(int nspan, int slices) { return fit_slices_legal(nspan, slices) ? 1 : 0; }
+extern "C" int hostcheck_fit_total_parts(long long m) { return fit_total_parts(m); }
+// 0 when the inspection entry points accept these samples and knots
+extern "C" int hostcheck_fit_samples_knots_wrong(long long m, const double* u, int n, const double* t) { return fit_samples_knots_wrong(m, u, n, t) ? 1 : 0; }
+
 // host build of the PnP math (mvus_amd/csrc/pnp.hip.h)
 extern "C" int hostcheck_pnp_dlt6(const double* Xs /* [6][3] */, const double* xn /* [6][2] */, double* R, double* t) {
   return pnp_dlt6(reinterpret_cast<const double (*)[3]>(Xs), reinterpret_cast<const double (*)[2]>(xn), R, t) ? 1 : 0;

@@ -58,6 +58,12 @@ def load():
     lib.hostcheck_band_at.argtypes = [ctypes.c_int] * 5 + [ctypes.c_longlong] + [_lib.c_int32_p] * 3 + [_lib.c_int64_p]
     lib.hostcheck_band_parts_sweep.restype = None
     lib.hostcheck_band_parts_sweep.argtypes = [ctypes.c_int] * 4 + [_lib.c_int64_p]
+    lib.hostcheck_fit_constants.restype = None
+    lib.hostcheck_fit_constants.argtypes = [_lib.c_int64_p]
+    lib.hostcheck_fit_slices.argtypes = [ctypes.c_int]
+    lib.hostcheck_fit_slices_legal.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.hostcheck_fit_total_parts.argtypes = [ctypes.c_longlong]
+    lib.hostcheck_fit_samples_knots_wrong.argtypes = [ctypes.c_longlong, _lib.c_double_p, ctypes.c_int, _lib.c_double_p]
     lib.hostcheck_pnp_dlt6.argtypes = [_lib.c_double_p] * 4
     lib.hostcheck_pnp_project.argtypes = [_lib.c_double_p] * 6
     lib.hostcheck_pnp_point_normal.argtypes = [_lib.c_double_p] * 5 + [ctypes.c_double, ctypes.c_double, _lib.c_double_p]
