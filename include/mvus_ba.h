@@ -366,6 +366,41 @@ int32_t mvus_ba_covariance_stage_ms(mvus_ba* h, double* ms_out, const char** nam
  * max_iter); MVUS_SOLVER_LM_SCHUR does not re-linearise the accepted point when max_nfev stops it. */
 int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_result* res, double* f_out);
 
+/* Register cameras against a HELD trajectory: a batch of B small, independent least-squares problems, each solved by Levenberg-Marquardt
+ * entirely on the device (one read-back at the end of the call).  Problem b is (camera cam[b] of the handle, start vector start[b]): its
+ * 3 + P unknowns are that camera's alpha, beta, rs and P parameters -- the order of one camera's entries in mvus_ba_set_frozen -- and the
+ * control points are those of x[n], constants.  It minimises 0.5 sum rho over the camera's 2 M_c detection rows only (motion rows and
+ * position priors do not involve a camera): visibility is evaluated at every point, switched-off groups (opt_sync = 0, rs_free = 0) have
+ * zero columns, the handle's frozen mask restricted to the camera holds further entries (g_k = 0, row and column zero, H_kk = 1; the value
+ * returns with the bits it went in with), the handle's loss (mvus_ba_set_loss) is in force with scipy's row scaling as in the LM + Schur
+ * assembly, and under rs_bounds the trial point is projected onto 0 <= rs <= 1 (a held rs has no box).  The LM rules are those of
+ * MVUS_SOLVER_LM_SCHUR per problem: D = diag(H) (1 where 0), (H + lambda D) p = -g by Cholesky, lambda_0 = max(lambda0 > 0 ? lambda0 : 1e-4,
+ * lambda_min), Nielsen's update on a gain, lambda *= nu, nu *= 2 on none, a failed factorisation (x 10) or a non-finite trial cost (x nu)
+ * raises lambda up to 1e12, no trust region; termination, nfev and status 0 - 4 follow scipy's check_termination, |x| in the xtol test being
+ * the norm of the problem's own 3 + P vector.  Status -1: the problem was never started (non-finite cost at the start, or fewer rows with a
+ * Jacobian -- two per visible detection -- than free unknowns).
+ *   start[B * (3 + P)]: alpha, beta, rs, then the P parameters of each problem; NULL = every problem starts from x's entries of its camera.
+ * Outputs (any may be NULL): cam_out[B * (3 + P)] the result of each problem; cost_out / cost0_out[B] the (robust) cost at the result and at
+ * the start; nfev_out, status_out[B]; visible_out[B] detections with a span at the result; inliers_out[B] visible detections with
+ * sqrt(ex^2 + ey^2) < inlier_thres at the result (the score of remove_outliers; it cannot be raised by sliding the camera out of the
+ * trajectory's time range, as the cost can be lowered), not computed (0) when inlier_thres <= 0.
+ * A problem's result has the same bits alone, anywhere in any batch, and from run to run.  Both calls work in buffers of their own: the
+ * held Jacobian, what an LM solve carried over, the damping history and the blocks of mvus_ba_normal_equations stay as they are -- a later
+ * mvus_ba_solve returns the bits it would have returned without the call.
+ * MVUS_E_INVALID before the device is touched: B < 0, B > 4096, a camera index outside [0, C), a non-finite start, max_nfev < 1, a negative
+ * tolerance (B == 0 is MVUS_OK and does nothing).  MVUS_E_NUMERIC: an rs start outside [0, 1] under rs_bounds unless held, as mvus_ba_solve
+ * treats x0.  MVUS_E_UNSUPPORTED on a sharded handle ("sharded" in the message).  No CPU fallback.  No reference counterpart. */
+int mvus_ba_register_cameras(mvus_ba* h, const double* x, int32_t B, const int32_t* cam, const double* start,
+                             int32_t max_nfev, double ftol, double xtol, double gtol, double lambda0, double lambda_min, double inlier_thres,
+                             double* cam_out, double* cost_out, double* cost0_out, int32_t* nfev_out, int32_t* status_out,
+                             int64_t* visible_out, int64_t* inliers_out);
+/* Inspection hook of the above (like mvus_ba_lsmr): the normal equations of each problem at its start point exactly as the first iteration
+ * of the solver forms them, by the same kernels -- H_out[B][(3 + P)^2] full symmetric (held entries: row and column zero, H_kk = 1;
+ * switched-off ones: zero), g_out[B][3 + P], cost_out[B] the (robust) cost and visible_out[B] at the start points.  Arguments, errors and
+ * what it leaves alone as above. */
+int mvus_ba_register_linearize(mvus_ba* h, const double* x, int32_t B, const int32_t* cam, const double* start,
+                               double* H_out, double* g_out, double* cost_out, int64_t* visible_out);
+
 /* Scene.remove_outliers (common.py:700-717): keep[i] = sqrt(ex^2 + ey^2) < thres, camera-segmented order. */
 int mvus_ba_outlier_mask(mvus_ba* h, const double* x, double thres, uint8_t* keep);
 

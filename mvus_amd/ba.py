@@ -390,6 +390,45 @@ class BAHandle:
                        optimality=res.optimality, lin_iters=res.lin_iters, solve_ms=res.solve_ms,
                        initial_cost=res.initial_cost, success=res.status > 0, grad=None, jac=None)
 
+    def _register_args(self, x, cams, start):
+        x = self._x(x, self.n)
+        cams = np.ascontiguousarray(np.atleast_1d(cams), dtype=np.int32).ravel()
+        B, nb = cams.size, 3 + self.prob.P
+        if start is not None:
+            start = np.ascontiguousarray(start, dtype=np.float64).reshape(-1, nb) if np.size(start) else np.empty((0, nb))
+            if start.shape != (B, nb):
+                raise ValueError('start has shape %s, expected (%d, %d)' % (start.shape, B, nb))
+        return x, cams, start, B, nb
+
+    def register_cameras(self, x, cams, start=None, max_nfev=50, ftol=1e-8, xtol=1e-12, gtol=1e-8, lambda0=0, lambda_min=0, inlier_thres=0):
+        """Register cameras against the trajectory of ``x``, which stays as it is (mvus_ba_register_cameras): problem b adjusts camera
+        ``cams[b]``'s alpha, beta, rs and P parameters from ``start[b]`` (3 + P values in that order; ``None``: the camera's entries of x)
+        over its own detection rows, by Levenberg-Marquardt on the device, all problems in one call.  The handle's loss and frozen mask
+        are in force.  Returns a namespace of arrays: ``params`` (B, 3 + P), ``cost``, ``initial_cost``, ``nfev``, ``status`` (scipy's 0 - 4,
+        -1 = never started), ``visible`` and ``inliers`` (detections with a span / with an error below ``inlier_thres`` at the result).
+        Changes nothing a later solve sees."""
+        x, cams, start, B, nb = self._register_args(x, cams, start)
+        params, cost, cost0 = np.zeros((B, nb)), np.zeros(B), np.zeros(B)
+        nfev, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        vis, inl = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+        i32, i64 = (lambda a: a.ctypes.data_as(_lib.c_int32_p)), (lambda a: a.ctypes.data_as(_lib.c_int64_p))
+        self._check(self.lib.mvus_ba_register_cameras(
+            self.h, _lib.dptr(x), B, i32(cams), _lib.dptr(start) if start is not None else None, int(max_nfev), float(ftol), float(xtol),
+            float(gtol), float(lambda0), float(lambda_min), float(inlier_thres), _lib.dptr(params), _lib.dptr(cost), _lib.dptr(cost0),
+            i32(nfev), i32(status), i64(vis), i64(inl)), 'mvus_ba_register_cameras')
+        return SimpleNamespace(params=params, cost=cost, initial_cost=cost0, nfev=nfev, status=status, visible=vis, inliers=inl)
+
+    def register_linearize(self, x, cams, start=None):
+        """(H (B, 3 + P, 3 + P), g (B, 3 + P), cost (B,), visible (B,)) of the registration problems at their start points, exactly as the
+        first iteration of ``register_cameras`` forms them (mvus_ba_register_linearize)."""
+        x, cams, start, B, nb = self._register_args(x, cams, start)
+        H, g, cost = np.zeros((B, nb, nb)), np.zeros((B, nb)), np.zeros(B)
+        vis = np.zeros(B, dtype=np.int64)
+        self._check(self.lib.mvus_ba_register_linearize(
+            self.h, _lib.dptr(x), B, cams.ctypes.data_as(_lib.c_int32_p), _lib.dptr(start) if start is not None else None,
+            _lib.dptr(H), _lib.dptr(g), _lib.dptr(cost), vis.ctypes.data_as(_lib.c_int64_p)), 'mvus_ba_register_linearize')
+        return H, g, cost, vis
+
     def outlier_mask(self, x, thres):
         """Per-detection ``error < thres`` (camera-segmented order), dtype bool."""
         x = self._x(x, self.n)

@@ -18,6 +18,7 @@
 #include "ba_schur_hip.hip.h"
 #include "ba_schur_host.hip.h"
 #include "ba_cov.hip.h"
+#include "ba_register.hip.h"
 
 namespace mvus {
 
@@ -34,6 +35,7 @@ struct mvus_ba {
   HipBackend be;
   std::unique_ptr<HipSchur<HipBackend>> schur;   // normal-equation workspace, built on first use
   std::unique_ptr<CovChain<HipBackend>> cov;     // buffers of mvus_ba_covariance (ba_cov.hip.h), built on first use
+  std::unique_ptr<RegisterWork> reg;             // buffers of mvus_ba_register_cameras / _linearize (ba_register.hip.h), built on first use
   mvus_rccl_handle rccl;                         // communicator of mvus_ba_set_rccl (destroyed with the handle)
   ~mvus_ba();
 };
@@ -724,6 +726,47 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
   });
 }
 
+// The two registration entry points share everything but the schedule's length and the outputs.  The scalar arguments are checked before
+// the handle is looked at (so a NULL handle still gets their message, through mvus_last_error(NULL)), the batch against C and P next, and
+// only then is the device touched.
+static int register_call(mvus_ba* h, const char* who, const double* x, int32_t B, const int32_t* cam, const double* start, RegOpts o,
+                         bool linearize_only, const RegisterOutputs& out) {
+  char msg[160];
+  if (reg_check_scalars(who, B, o.max_nfev, o.ftol, o.xtol, o.gtol, msg, sizeof msg)) {
+    if (h) h->be.err = msg; else g_create_error = msg;
+    return MVUS_E_INVALID;
+  }
+  if (B == 0) return MVUS_OK;                    // nothing to do: no state is looked at
+  if (!h) { g_create_error = std::string(who) + ": NULL handle"; return MVUS_E_INVALID; }
+  return guarded(h, [&] {
+    HipBackend& be = h->be;
+    // nothing the handle holds is touched: what an LM solve left for the very next call stays valid for the call after this one
+    if (be.carry_seq + 1 == be.api_seq) be.carry_seq = be.api_seq;
+    if (h->schur) h->schur->carry_held();
+    if (reg_check_batch(who, be.hp.C, be.hp.P, B, cam, start, msg, sizeof msg)) { be.err = msg; return MVUS_E_INVALID; }
+    if (!x) { be.err = std::string(who) + ": x is NULL"; return MVUS_E_INVALID; }
+    if (be.allreduce || be.tshard.on) { be.err = std::string(who) + ": not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
+    if (!h->reg) h->reg.reset(new RegisterWork());
+    return register_run(be, *h->reg, x, B, cam, start, o, linearize_only, out);
+  });
+}
+
+int mvus_ba_register_cameras(mvus_ba* h, const double* x, int32_t B, const int32_t* cam, const double* start,
+                             int32_t max_nfev, double ftol, double xtol, double gtol, double lambda0, double lambda_min, double inlier_thres,
+                             double* cam_out, double* cost_out, double* cost0_out, int32_t* nfev_out, int32_t* status_out,
+                             int64_t* visible_out, int64_t* inliers_out) {
+  const RegOpts o{max_nfev, 0, ftol, xtol, gtol, lambda0, lambda_min >= 0 ? lambda_min : 0.0, inlier_thres};
+  const RegisterOutputs out{cam_out, cost_out, cost0_out, nfev_out, status_out, visible_out, inliers_out, nullptr, nullptr};
+  return register_call(h, "register_cameras", x, B, cam, start, o, false, out);
+}
+
+int mvus_ba_register_linearize(mvus_ba* h, const double* x, int32_t B, const int32_t* cam, const double* start,
+                               double* H_out, double* g_out, double* cost_out, int64_t* visible_out) {
+  const RegOpts o{1, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const RegisterOutputs out{nullptr, nullptr, cost_out, nullptr, nullptr, visible_out, nullptr, H_out, g_out};
+  return register_call(h, "register_linearize", x, B, cam, start, o, true, out);
+}
+
 int mvus_ba_outlier_mask(mvus_ba* h, const double* x, double thres, uint8_t* keep) {
   return guarded(h, [&] {
     HipBackend& be = h->be;
@@ -801,6 +844,7 @@ int mvus_ba_set_allreduce(mvus_ba* h, mvus_allreduce_fn fn, void* user, int32_t 
 
 }  // extern "C"
 mvus_ba::~mvus_ba() {
+  reg.reset();
   cov.reset();
   schur.reset();
   if (rccl.comm && g_rccl.CommDestroy) { (void)hipStreamSynchronize(be.stream); (void)g_rccl.CommDestroy(rccl.comm); }

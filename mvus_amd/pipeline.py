@@ -39,7 +39,9 @@ def incremental_reconstruction(flight, max_iter=10, verbose=False, timer=None):
     poses and whose ``spline`` holds the first trajectory; the remaining cameras have ``P is None``.  Uses the settings keys
     of the reference's config.json: rolling_shutter, motion_reg, motion_weights, rs_bounds, thres_outlier,
     thres_triangulation, smooth_factor, sampling_rate, thres_PnP (optional, default 8 as in get_camera_pose).  With the opt-in
-    ``ba_solver: 'lm'`` and no ``ba_lambda_min`` the loop sets its own damping floor (0.3) in ``flight.settings``.
+    ``ba_solver: 'lm'`` and no ``ba_lambda_min`` the loop sets its own damping floor (0.3) in ``flight.settings``.  With the opt-in
+    ``ba_register: true`` every new camera is registered against the trajectory as it stands (``Scene.register_camera``, with the starts
+    of ``ba_register_beta_search`` when given) between ``get_camera_pose`` and ``triangulate``, as a stage of its own.
     Returns the StageTimer."""
     timer = timer or StageTimer()
     st = flight.settings
@@ -59,6 +61,7 @@ def incremental_reconstruction(flight, max_iter=10, verbose=False, timer=None):
 
 def _incremental_loop(flight, st, max_iter, verbose, timer):
     kw = dict(rs=st['rolling_shutter'], motion_reg=st['motion_reg'], motion_weights=st['motion_weights'], rs_bounds=st['rs_bounds'])
+    register, beta_search = flight.ba_register_enabled(), flight.ba_register_beta_search()      # (validated before the first BA)
     cam_temp = 2
     while True:
         seq = flight.sequence[:cam_temp]
@@ -76,6 +79,11 @@ def _incremental_loop(flight, st, max_iter, verbose, timer):
         timer.run('select_most_overlap', cam_temp, flight.select_most_overlap)
         nxt = flight.sequence[cam_temp]
         timer.run('get_camera_pose', cam_temp, flight.get_camera_pose, nxt, error=st.get('thres_PnP', 8))
+        if register:
+            # the PnP pose was computed with whatever alpha, beta, rs the camera had: adjust the camera against the trajectory as it
+            # stands before its detections are triangulated into it
+            timer.run('register_camera', cam_temp, flight.register_camera, nxt, beta_search=beta_search, rs=st['rolling_shutter'],
+                      rs_bounds=st['rs_bounds'])
         timer.run('triangulate', cam_temp, flight.triangulate, nxt, flight.sequence[:cam_temp], thres=st['thres_triangulation'],
                   factor_t2s=st['smooth_factor'], factor_s2t=st['sampling_rate'])
         cam_temp += 1

@@ -51,6 +51,11 @@ Extra ``settings`` keys (all optional; a reference ``config.json`` has none of t
                (``Scene.align_to_position_priors``) and ends with one LM BA over all cameras that carries them.  Not with 'trf'
                (ValueError), and a problem the wide-band policy above would hand to TRF raises instead of dropping the priors.  DEFAULT
                False: nothing changes.
+``ba_register`` True: the incremental loop of ``mvus_amd.pipeline`` calls ``Scene.register_camera`` on every new camera between
+               ``get_camera_pose`` and ``triangulate``: alpha, beta, rs and the pose of THAT camera are adjusted against the trajectory as it
+               stands (``mvus_ba_register_cameras``: Levenberg-Marquardt per camera on the device), the spline and the other cameras
+               untouched.  ``ba_register_beta_search`` [half_width, step] (frames, optional) makes it start from beta + k step,
+               |k step| <= half_width, all in one call, and keep the start with the most inliers.  DEFAULT False: nothing changes.
 ``ba_deterministic`` accepted and ignored: the 'lm' solver's normal equations are assembled without floating-point atomics
                (one writer, one order of additions per entry) -- the same bits on every run by construction.
 ``opt_sync`` (reference key: False freezes alpha/beta), ``device``.
@@ -532,6 +537,8 @@ class Scene:
         self.ba_freeze()                     # (and ba_freeze / ba_gauge)
         self.ba_covariance_enabled()         # (and ba_covariance)
         self.ba_kinematics_enabled()         # (and ba_kinematics)
+        self.ba_register_enabled()           # (and ba_register / ba_register_beta_search)
+        self.ba_register_beta_search()
         self.ba_position_priors()            # (and ba_position_priors / Scene.position_priors)
         return solver, modes[jac]
 
@@ -643,6 +650,121 @@ class Scene:
         if not isinstance(v, (bool, np.bool_)):
             raise ValueError("settings['ba_kinematics'] must be true or false, not %r" % (v,))
         return bool(v)
+
+    def ba_register_enabled(self):
+        """settings['ba_register'] validated (a bool; absent = False): host only.  True makes the incremental loop register every new
+        camera against the held trajectory (``register_camera``) between ``get_camera_pose`` and ``triangulate``."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        v = st.get('ba_register', False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("settings['ba_register'] must be true or false, not %r" % (v,))
+        return bool(v)
+
+    def ba_register_beta_search(self):
+        """settings['ba_register_beta_search'] validated: absent / None -> None, else (half_width, step) in frames, two finite numbers with
+        half_width >= 0 and step > 0.  Host only."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        v = st.get('ba_register_beta_search', None)
+        if v is None:
+            return None
+        ok = isinstance(v, (list, tuple)) and len(v) == 2 and all(
+            not isinstance(q, (bool, np.bool_)) and isinstance(q, (int, float, np.integer, np.floating)) and np.isfinite(q) for q in v)
+        if not ok or not (v[0] >= 0 and v[1] > 0):
+            raise ValueError("settings['ba_register_beta_search'] must be [half_width, step] in frames (finite, half_width >= 0, step > 0), "
+                             "not %r" % (v,))
+        return float(v[0]), float(v[1])
+
+    @staticmethod
+    def register_rank(status, inliers, cost, ks):
+        """The order in which ``register_camera`` prefers the starts of one call: the ones that started (status >= 0) only; most inliers
+        first, then the lowest cost, then the smallest |k| (the start nearest the camera's own beta), then the lower index.  A list of
+        indices, empty when no problem started.  Host only."""
+        started = [b for b in range(len(status)) if int(status[b]) >= 0]
+        return sorted(started, key=lambda b: (-int(inliers[b]), float(cost[b]), abs(int(ks[b])), b))
+
+    def register_camera(self, cam_id, beta_search=None, hold=('K', 'd'), rs=False, rs_bounds=False, thres=None, max_nfev=50, keep_start=True):
+        """Adjust ONE camera -- alpha, beta, rs and its pose (and K, d under ``opt_calib``) -- against the trajectory as it stands
+        (``mvus_ba_register_cameras``): ``self.spline`` and every other camera are left alone.  The camera needs a pose (``get_camera_pose``).
+        ``hold``: names of ``ba_freeze`` (alpha beta rs R t K d; K, d only exist under ``opt_calib``) kept where they are.
+        ``beta_search = (half_width, step)`` in frames: the starts ``beta + k step``, ``|k step| <= half_width``, all solved in ONE call;
+        the winner has the most inliers at ``thres`` (default ``settings['thres_outlier']``), then the lowest cost, then the smallest
+        ``|k|``.  ``Scene.ba_loss()`` is in force.  Writes alpha, beta, rs, R, t (K, d when free) back and returns the namespace of
+        ``BAHandle.register_cameras`` plus ``chosen`` (the winning index) and ``starts``.
+        ``keep_start`` (default on; off = the winner is always written back): the camera as it came in is scored the same way (one more
+        evaluation: ``start_inliers``), and a winner with FEWER inliers at ``thres`` than that is NOT written back -- ``kept_start`` says
+        so, and the call prints it.  The camera's detections have not been through ``remove_outliers``: least squares under the linear
+        loss gives way to gross outliers that PnP + RANSAC ignored (a robust ``ba_loss`` is the remedy, and then the winner is kept)."""
+        cam_id = int(cam_id)
+        st = self.settings if isinstance(self.settings, dict) else {}
+        calib = bool(st.get('opt_calib', False))
+        hold = tuple(hold) if hold is not None else ()
+        for name in hold:
+            if not isinstance(name, str) or name not in self.FREEZE_NAMES:
+                raise ValueError('register_camera: unknown name %r in hold (one of %s)' % (name, list(self.FREEZE_NAMES)))
+        if beta_search is not None:
+            if len(beta_search) != 2 or not (np.isfinite(beta_search[0]) and np.isfinite(beta_search[1]) and beta_search[0] >= 0 and beta_search[1] > 0):
+                raise ValueError('register_camera: beta_search must be (half_width, step) in frames with half_width >= 0 and step > 0, not %r' % (beta_search,))
+        cam = self.cameras[cam_id]
+        if getattr(cam, 'R', None) is None or getattr(cam, 't', None) is None:
+            raise ValueError('register_camera: camera %d has no pose yet (get_camera_pose first)' % cam_id)
+        if not getattr(self, 'spline', None) or not self.spline.get('tck'):
+            raise ValueError('register_camera: the scene has no trajectory spline')
+        loss, f_scale = self.ba_loss()
+        self.alpha, self.beta, self.rs = (np.asarray(v, dtype=np.float64) for v in (self.alpha, self.beta, self.rs))
+        prob = self._ba_problem([cam_id], rs=rs, rs_bounds=rs_bounds)
+        x = self._pack(prob, [cam_id])
+        P = prob.P
+        part = {'K': range(0, 4), 'R': range(4, 7), 't': range(7, 10), 'd': range(10, 15)} if calib else {'R': range(0, 3), 't': range(3, 6)}
+        mask = np.zeros(3 + P, dtype=bool)
+        for name in hold:
+            if name in ('alpha', 'beta', 'rs'):
+                mask[('alpha', 'beta', 'rs').index(name)] = True
+            elif name in part:                       # (K, d without opt_calib are not in x: held by construction)
+                mask[[3 + j for j in part[name]]] = True
+        start = x[:3 + P].copy()[None, :]
+        if beta_search is not None:
+            kmax = int(np.floor(beta_search[0] / beta_search[1] + 1e-9))
+            ks = np.arange(-kmax, kmax + 1)
+            start = np.repeat(start, ks.size, axis=0)
+            start[:, 1] += ks * float(beta_search[1])
+        else:
+            ks = np.zeros(1, dtype=np.int64)
+        thres = float(st.get('thres_outlier', 0) if thres is None else thres)
+        with self._handle(prob) as h:
+            if (loss, f_scale) != h.loss:
+                h.set_loss(loss, f_scale)
+            if mask.any():
+                h.set_frozen(mask)
+            res = h.register_cameras(x, np.zeros(start.shape[0], dtype=np.int32), start=start, max_nfev=max_nfev, inlier_thres=thres)
+            # the camera as it came in, scored the same way (one evaluation, nothing moves)
+            came = h.register_cameras(x, [0], max_nfev=1, inlier_thres=thres) if (keep_start and thres > 0) else None
+        order = self.register_rank(res.status, res.inliers, res.cost, ks)
+        if not order:
+            raise ValueError('register_camera: camera %d has too few detections on the trajectory for its %d free parameters' % (cam_id, int((~mask).sum())))
+        best = int(order[0])
+        res.chosen, res.starts = best, start
+        # The camera's detections have not been through remove_outliers yet.  Under the linear loss a few gross outliers can pull the
+        # least-squares estimate away from what PnP + RANSAC found (the rms falls, the typical error rises): a result that explains FEWER
+        # detections within ``thres`` than the camera did as it came in is not written back.
+        res.start_inliers = int(came.inliers[0]) if came is not None else None
+        res.kept_start = bool(came is not None and res.start_inliers > int(res.inliers[best]))
+        if res.kept_start:
+            print('register_camera: camera %d keeps the state it came in with (%d inliers at %g px; the registered one has %d)'
+                  % (cam_id, res.start_inliers, thres, int(res.inliers[best])))
+            return res
+        xb = x.copy()
+        xb[:3 + P] = res.params[best]
+        alpha, beta, rs_new, cam_states, _ = _problem.unpack_x(prob, xb)
+        self.alpha[cam_id], self.beta[cam_id], self.rs[cam_id] = alpha[0], beta[0], rs_new[0]
+        for name in ('K', 'd') if calib else ():     # (a held part keeps the object it has: no round trip through x)
+            if name not in hold:
+                setattr(cam, name, cam_states[0][name])
+        for name in ('R', 't'):
+            if name not in hold:
+                setattr(cam, name, cam_states[0][name])
+        cam.compose()
+        self.detection_to_global(cam_id)
+        return res
 
     def kinematics(self, t=None, fps=None, cov=None):
         """Velocity, acceleration, speed and distance flown along the trajectory splines at timestamps ``t`` (default: the stamps of
