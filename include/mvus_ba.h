@@ -147,7 +147,7 @@ void mvus_default_opts(mvus_solve_opts* opts);
  * sizeof(mvus_result), sizeof(mvus_problem) as this library was compiled (any pointer may be NULL) and returns MVUS_ABI_VERSION.  A
  * binding asserts these against its own struct definitions at load time -- mvus_solve_opts has grown over the rounds (lm_lambda_min,
  * lm_trust_radius) and a stale stub would otherwise hand the library a short buffer.  The version is raised whenever a struct or an
- * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance, mvus_ba_set_position_priors) does not raise
+ * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance, mvus_ba_set_position_priors, mvus_ba_detection_covariance) does not raise
  * it -- a binding that needs one finds it missing at load time.  Stateless, no device is touched.  No reference counterpart (the reference has no FFI). */
 #define MVUS_ABI_VERSION 8
 int32_t mvus_abi_sizes(int32_t* solve_opts_size, int32_t* result_size, int32_t* problem_size);
@@ -356,6 +356,28 @@ int mvus_ba_covariance(mvus_ba* h, const double* x, double sigma2, double* cov_c
 /* Measurement hook: milliseconds (HIP events) of the stages of the LAST mvus_ba_covariance on the handle and their names, the first `count`
  * of them; returns the number of stages, or MVUS_E_INVALID before the first call. */
 int32_t mvus_ba_covariance_stage_ms(mvus_ba* h, double* ms_out, const char** names_out, int32_t count);
+
+/* The covariance carried back to the image plane (ba_detcov.hip.h): per detection the covariance of its fitted value and its studentised
+ * residual, at x, with the loss, the frozen mask and the position priors in force.  Sigma is EXACTLY the matrix mvus_ba_covariance defines.
+ * For detection i of camera c with a knot span, J_i = the two rows of the analytic Jacobian (raw: the loss does not scale them; frozen
+ * columns contribute nothing, Sigma is zero there), Pi_i = J_i Sigma J_i^T -- which needs the camera-trajectory cross-covariance the
+ * library keeps to itself.  Outputs (any may be NULL), detections in camera-segmented order as for mvus_ba_residual_jacobian:
+ *   e_out[2M] = u(M) v(M): the SIGNED residual in pixels, predicted minus observed; |e| is bit for bit the two rows of f of the detection;
+ *   pcov_out[3M] = uu(M) uv(M) vv(M): P = D Pi_i D, D = diag(sign e_u, sign e_v) -- the covariance of the fitted detection in image axes
+ *     (its 1-sigma ellipse).  With opt_calib and undist_points the observed point is undistorted with the unknown intrinsics and so
+ *     depends on x too: P is then the covariance of the fitted part of the residual in the undistorted frame, not of a bare projection;
+ *   t2_out[M] = r^T (sigma^2 I - Pi_i)^-1 r, r = |e|: the squared studentised residual (independent of the signs), NaN when
+ *     sigma^2 I - Pi_i is not positive definite.  chi^2 with 2 degrees of freedom under the linear loss only; under a robust loss it is
+ *     the Gauss-Newton approximation described above.
+ * A detection without a span: NaN in pcov_out and t2_out, 0 in e_out.
+ * cov_cam, cov_band, estimated, sigma2_out, dof_out: exactly what mvus_ba_covariance returns for the same arguments (one run of the chain
+ * serves both).  Refusals and side effects are those of mvus_ba_covariance, the messages prefixed "detection_covariance:".  The first call
+ * allocates one more buffer of 3N x CB doubles (T = Z Sigma_cc); MVUS_E_HIP when that fails. */
+int mvus_ba_detection_covariance(mvus_ba* h, const double* x, double sigma2, double* e_out, double* pcov_out, double* t2_out, double* cov_cam,
+                                 double* cov_band, uint8_t* estimated, double* sigma2_out, int64_t* dof_out);
+/* Measurement hook: milliseconds (HIP events) of the detection pass of the LAST mvus_ba_detection_covariance on the handle; MVUS_E_INVALID
+ * before the first such call. */
+int32_t mvus_ba_detection_covariance_ms(mvus_ba* h, double* ms_out);
 
 /* The least_squares call of Scene.BA (common.py:670) -- x is read and overwritten with res.x.
  * lb/ub come from opts of the problem (rs_bounds).  f_out[m] may be NULL.  x, res and f_out are complete on return.  MVUS_SOLVER_LM_SCHUR

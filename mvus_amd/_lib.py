@@ -94,6 +94,9 @@ API = [
     ('mvus_ba_robust_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
     ('mvus_ba_covariance', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_double_p, c_double_p, c_uint8_p, c_double_p, c_int64_p]),
     ('mvus_ba_covariance_stage_ms', ctypes.c_int32, [ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32]),
+    ('mvus_ba_detection_covariance', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p,
+                                                   c_double_p, c_int64_p]),
+    ('mvus_ba_detection_covariance_ms', ctypes.c_int32, [ctypes.c_void_p, c_double_p]),
     ('mvus_ba_solve', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.POINTER(MvusSolveOpts), ctypes.POINTER(MvusResult), c_double_p]),
     ('mvus_ba_register_cameras', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int32, c_int32_p, c_double_p, ctypes.c_int32] + [ctypes.c_double] * 6
                                                + [c_double_p] * 3 + [c_int32_p] * 2 + [c_int64_p] * 2),

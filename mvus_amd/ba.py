@@ -359,6 +359,33 @@ class BAHandle:
         self._check(min(k, 0), 'mvus_ba_covariance_stage_ms')
         return [(names[i].decode(), ms[i]) for i in range(k)]
 
+    def detection_covariance(self, x, sigma2=None):
+        """The covariance at x carried back to the image plane (mvus_ba_detection_covariance): the namespace of ``covariance`` -- the same
+        bits, one run of the chain -- plus, per detection in camera-segmented order (M = all detections),
+        ``e`` [2, M] the signed residual (u, v) in pixels, predicted minus observed (``abs(e)`` is the detection's two rows of ``residual``),
+        ``cov`` [3, M] = (P_uu, P_uv, P_vv) of P = J_i Sigma J_i^T in image axes (the 1-sigma ellipse of the fitted detection; with
+        ``opt_calib`` and ``undist_points`` the observed point moves with the intrinsics too, and P is the covariance of the fitted part of
+        the residual in the undistorted frame), and ``t2`` [M] = r^T (sigma2 I - P)^-1 r, the squared studentised residual (chi^2 with 2
+        degrees of freedom under the linear loss; NaN when sigma2 I - P is not positive definite).  A detection without a knot span has NaN
+        in ``cov`` and ``t2`` and 0 in ``e``.  Refusals as for ``covariance``."""
+        x = self._x(x, self.n)
+        CB, N, M = self.prob.C * (3 + self.prob.P), int(self.prob.n_coef.sum()), int(self.M)
+        cam = np.empty((CB, CB))
+        band = np.empty((N, 4, 3, 3))
+        est = np.empty(self.n, dtype=np.uint8)
+        e, pc, t2 = np.zeros((2, M)), np.full((3, M), np.nan), np.full(M, np.nan)
+        s2, dof = ctypes.c_double(0.0), ctypes.c_int64(0)
+        self._check(self.lib.mvus_ba_detection_covariance(self.h, _lib.dptr(x), 0.0 if sigma2 is None else float(sigma2), _lib.dptr(e), _lib.dptr(pc),
+                                                          _lib.dptr(t2), _lib.dptr(cam), _lib.dptr(band), est.ctypes.data_as(_lib.c_uint8_p),
+                                                          ctypes.byref(s2), ctypes.byref(dof)), 'mvus_ba_detection_covariance')
+        return SimpleNamespace(e=e, cov=pc, t2=t2, cam=cam, band=band, estimated=est.astype(bool), sigma2=s2.value, dof=int(dof.value))
+
+    def detection_covariance_ms(self):
+        """Milliseconds (HIP events) of the detection pass of the last ``detection_covariance`` call on the handle."""
+        ms = ctypes.c_double(0.0)
+        self._check(self.lib.mvus_ba_detection_covariance_ms(self.h, ctypes.byref(ms)), 'mvus_ba_detection_covariance_ms')
+        return ms.value
+
     def solve(self, x0, solver=SOLVER_TRF_LSMR, jac_mode=JAC_PATTERN, max_nfev=10, opts=None, return_fun=True,
               ties='numpy', matrix=None, prepared=False):
         """The least_squares call of Scene.BA.  Returns an OptimizeResult-like namespace

@@ -34,7 +34,7 @@ struct mvus_rccl_handle { void* comm = nullptr; };
 struct mvus_ba {
   HipBackend be;
   std::unique_ptr<HipSchur<HipBackend>> schur;   // normal-equation workspace, built on first use
-  std::unique_ptr<CovChain<HipBackend>> cov;     // buffers of mvus_ba_covariance (ba_cov.hip.h), built on first use
+  std::unique_ptr<CovChain<HipBackend>> cov;     // buffers of mvus_ba_covariance / mvus_ba_detection_covariance (ba_cov.hip.h), built on first use
   std::unique_ptr<RegisterWork> reg;             // buffers of mvus_ba_register_cameras / _linearize (ba_register.hip.h), built on first use
   mvus_rccl_handle rccl;                         // communicator of mvus_ba_set_rccl (destroyed with the handle)
   ~mvus_ba();
@@ -533,16 +533,18 @@ int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* w
   });
 }
 
-int mvus_ba_covariance(mvus_ba* h, const double* x, double sigma2, double* cov_cam, double* cov_band, uint8_t* estimated,
-                       double* sigma2_out, int64_t* dof_out) {
+// mvus_ba_covariance and mvus_ba_detection_covariance: one chain (CovChain::run), the second with the detection pass behind stage 8
+static int covariance_call(mvus_ba* h, const char* who, const double* x, double sigma2, const DetCovOut* det, double* cov_cam, double* cov_band,
+                           uint8_t* estimated, double* sigma2_out, int64_t* dof_out) {
   return guarded(h, [&] {
     HipBackend& be = h->be;
-    if (!x || !std::isfinite(sigma2)) { be.err = "covariance: x is NULL or sigma2 is not finite"; return MVUS_E_INVALID; }
-    if (be.allreduce || be.tshard.on) { be.err = "covariance: not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
+    const std::string pre = std::string(who) + ": ";
+    if (!x || !std::isfinite(sigma2)) { be.err = pre + "x is NULL or sigma2 is not finite"; return MVUS_E_INVALID; }
+    if (be.allreduce || be.tshard.on) { be.err = pre + "not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
     // what an LM solve left for its point (cost, blocks, the speculative linearisation) is dropped as mvus_ba_set_loss drops it -- the blocks
     // are overwritten below; the damping history stays: a later solve returns the bits it would have returned without this call
     be.carry = LmCarry{};
-    if (be.hp.C * (3 + be.hp.P) > 1152) { be.err = "covariance: more than 1152 camera-side unknowns"; return MVUS_E_UNSUPPORTED; }
+    if (be.hp.C * (3 + be.hp.P) > 1152) { be.err = pre + "more than 1152 camera-side unknowns"; return MVUS_E_UNSUPPORTED; }
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
     if (!h->cov) h->cov.reset(new CovChain<HipBackend>(be));
     // the (robust) cost at x, then the analytic Jacobian of x held as mvus_ba_residual_jacobian holds it
@@ -550,16 +552,34 @@ int mvus_ba_covariance(mvus_ba* h, const double* x, double sigma2, double* cov_c
     be.residual_sq(be.x_cur, be.f_cur, be.scal_out() + be.kCostSlot);
     double twice = 0;
     be.fetch(be.scal_out() + be.kCostSlot, 1, &twice);
-    if (!std::isfinite(twice)) { be.err = "covariance: residuals are not finite at x"; return MVUS_E_NUMERIC; }
+    if (!std::isfinite(twice)) { be.err = pre + "residuals are not finite at x"; return MVUS_E_NUMERIC; }
     be.jacobian(be.x_cur, be.f_cur, MVUS_JAC_ANALYTIC);
     be.held_analytic_at_xcur = true;
     CovResult res;
-    const int rc = h->cov->run(*h->schur, 0.5 * twice, sigma2, cov_cam, cov_band, estimated, res);
+    h->cov->who = who;
+    const int rc = h->cov->run(*h->schur, 0.5 * twice, sigma2, cov_cam, cov_band, estimated, res, det);
     if (rc != MVUS_OK) return rc;
     if (sigma2_out) *sigma2_out = res.sigma2;
     if (dof_out) *dof_out = res.dof;
     return MVUS_OK;
   });
+}
+
+int mvus_ba_covariance(mvus_ba* h, const double* x, double sigma2, double* cov_cam, double* cov_band, uint8_t* estimated,
+                       double* sigma2_out, int64_t* dof_out) {
+  return covariance_call(h, "covariance", x, sigma2, nullptr, cov_cam, cov_band, estimated, sigma2_out, dof_out);
+}
+
+int mvus_ba_detection_covariance(mvus_ba* h, const double* x, double sigma2, double* e_out, double* pcov_out, double* t2_out, double* cov_cam,
+                                 double* cov_band, uint8_t* estimated, double* sigma2_out, int64_t* dof_out) {
+  const DetCovOut det{e_out, pcov_out, t2_out};
+  return covariance_call(h, "detection_covariance", x, sigma2, &det, cov_cam, cov_band, estimated, sigma2_out, dof_out);
+}
+
+int32_t mvus_ba_detection_covariance_ms(mvus_ba* h, double* ms_out) {
+  if (!h || !h->cov || !h->cov->det_timed) return MVUS_E_INVALID;
+  if (ms_out) *ms_out = h->cov->det_ms;
+  return MVUS_OK;
 }
 
 int32_t mvus_ba_covariance_stage_ms(mvus_ba* h, double* ms_out, const char** names_out, int32_t count) {

@@ -19,15 +19,17 @@
 //                           Sigma_cc = S^-1 put back at full size with zero rows / columns
 //   6 k_cov_tz              T = Z Sigma_cc on the fp64 matrix cores, fused with the band of the low-rank term
 //                           R(p, p + w) = T_p Z_{p+w}^T, w <= 3: a tile of kCovTP control points plus a halo of nine rows of Z; T itself
-//                           is never stored
+//                           is never stored by mvus_ba_covariance (k_cov_tz<true> keeps it, for the detection pass only)
 //   7 k_cov_selinv          selected inverse of the band (Takahashi recurrence on the factor of stage 3), blocks w <= 3
 //   8 k_cov_band_out, k_cov_cam_out: sigma^2 (selected inverse + R) in control-point order; sigma^2 Sigma_cc in the order of the head of x
 // Stages 3, 5 (the panel's diagonal block) and 7 are sequential single-workgroup forms: the covariance is a one-off per BA.
+// Behind stage 8, on request (mvus_ba_detection_covariance): k_detcov, the per-detection pass of ba_detcov.hip.h, with an event pair of its own.
 // Refusal: a pivot p_k <= kCovPivotTol * H_kk of either factorisation (ba_cov_math.h) -> MVUS_E_NUMERIC naming the unknown.
 #pragma once
 #include <climits>
 
 #include "ba_cov_math.h"
+#include "ba_detcov.hip.h"
 #include "ba_schur_hip.hip.h"
 
 namespace mvus {
@@ -164,11 +166,17 @@ __global__ void k_cov_expand(int CB, int m, const int32_t* __restrict__ inv, con
 // [col0 + (l & 15)], accumulator entry r = T[(l >> 4) + 4 r][l & 15]; fragments straight from memory, everything outside the matrices
 // read as zero), the 48 x 16 piece of T and the 57 x 16 piece of Z (tile + halo) through the wavefront's own LDS, and each lane adds
 // that chunk's share to its nine of the tile's 16 x 4 x 9 entries of R.  The wavefronts' sums are added in a fixed order at the end.
+// STORE_T (launched with one more argument, Tm[N3][CB]): the wavefront also copies its 48 x 16 piece of T from LDS to Tm.  The
+// instantiation without it takes no such argument and is the kernel it was.
 constexpr int kCovTP = 16, kCovTR = 3 * kCovTP, kCovHalo = 9, kCovLd = 17;
 constexpr int kCovWaveLds = (2 * kCovTR + kCovHalo) * kCovLd;        // doubles per wavefront: T piece [48][17] + Z piece [57][17]
 constexpr int kCovTileOut = kCovTP * 36;
 static_assert(kCovTileOut == 9 * 64 && kCovTileOut <= kCovWaveLds, "nine entries of R per lane; the reduction reuses the staging space");
-__global__ __launch_bounds__(256) void k_cov_tz(int N, int CB, const double* __restrict__ Z, const double* __restrict__ Sig, double* __restrict__ Rb) {
+inline __device__ double* cov_tm_arg() { return nullptr; }
+inline __device__ double* cov_tm_arg(double* tm) { return tm; }
+template <bool STORE_T = false, class... TM>
+__global__ __launch_bounds__(256) void k_cov_tz(int N, int CB, const double* __restrict__ Z, const double* __restrict__ Sig, double* __restrict__ Rb, TM... tm_v) {
+  static_assert(sizeof...(TM) == (STORE_T ? 1 : 0), "the storing instantiation is launched with Tm, the other one without");
   __shared__ double lds[4 * kCovWaveLds];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
   const int N3 = 3 * N, p0 = blockIdx.x * kCovTP, r0 = 3 * p0;
@@ -204,6 +212,13 @@ __global__ __launch_bounds__(256) void k_cov_tz(int N, int CB, const double* __r
       Zt[rr * kCovLd + cc] = (row < N3 && col < CB) ? Z[(long long)row * CB + col] : 0.0;
     }
     __syncthreads();
+    if constexpr (STORE_T) {
+      double* __restrict__ Tm = cov_tm_arg(tm_v...);
+      for (int e = lane; e < kCovTR * 16; e += 64) {
+        const int rr = e >> 4, cc = e & 15, row = r0 + rr, col = j0 + cc;
+        if (row < N3 && col < CB) Tm[(long long)row * CB + col] = Tt[rr * kCovLd + cc];
+      }
+    }
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
       const int idx = lane + 64 * q, pl = idx / 36, w = (idx % 36) / 9, a = (idx % 9) / 3, b = idx % 3;
@@ -297,6 +312,14 @@ struct CovChain {
   double stage_ms[kCovStages] = {};
   bool timed = false;
   int N3 = 0, CB = 0, BW = 0;
+  // the detection pass (mvus_ba_detection_covariance): its buffers exist from the first such call on, with the event pair of the pass
+  DeviceOwner det_own;
+  const char* who = "covariance";   // the entry point the messages name
+  hipEvent_t det_ev[2] = {};
+  double det_ms = 0.0;
+  bool det_timed = false;
+  long long det_M = -1;
+  double *Tm = nullptr, *Gb = nullptr, *det_e = nullptr, *det_pcov = nullptr, *det_t2 = nullptr;
   double *diag = nullptr, *Lb = nullptr, *hs = nullptr, *Z = nullptr, *S = nullptr, *X = nullptr, *Sig = nullptr, *hc = nullptr, *Rb = nullptr, *sel = nullptr,
          *band_out = nullptr, *cam_out = nullptr;
   uint8_t* est = nullptr;
@@ -307,6 +330,7 @@ struct CovChain {
   void ensure(const NEView& ne, int bw) {
     if (Lb && N3 == ne.N3 && CB == ne.CB && BW == bw) return;
     own.reset(); Lb = nullptr;
+    det_own.reset(); Tm = nullptr; det_M = -1;
     N3 = ne.N3; CB = ne.CB; BW = bw;
     const size_t n3 = (size_t)N3, cb = (size_t)CB;
     diag = device<double>(cb + n3); est = device<uint8_t>(cb + n3);
@@ -320,26 +344,44 @@ struct CovChain {
     Lb = device<double>(n3 * (size_t)(bw + 1));               // (last: a non-null Lb says that everything above exists)
   }
   void mark(int s) { MVUS_HIP(hipEventRecord(ev[s], be.stream)); }
+  // Tm is as large as Z: its size (and the outputs') is bounded before anything is allocated, and a failed allocation leaves through
+  // MVUS_HIP as MVUS_E_HIP
+  int ensure_det(const NEView& ne, long long M) {
+    if (Tm && det_M == M) return MVUS_OK;
+    constexpr unsigned long long kMaxBytes = 1ull << 36;
+    const unsigned long long tm_bytes = (unsigned long long)ne.N3 * (unsigned long long)ne.CB * sizeof(double);
+    if (tm_bytes > kMaxBytes || (unsigned long long)M * 3 * sizeof(double) > kMaxBytes) { be.err = std::string(who) + ": T = Z Sigma_cc or the outputs exceed 64 GiB"; return MVUS_E_UNSUPPORTED; }
+    det_own.reset(); Tm = nullptr; det_M = -1;
+    const size_t m = (size_t)std::max<long long>(M, 1);
+    Gb = det_own.device<double>((size_t)ne.N * 36);
+    det_e = det_own.device<double>(2 * m); det_pcov = det_own.device<double>(3 * m); det_t2 = det_own.device<double>(m);
+    for (hipEvent_t& e : det_ev) e = det_own.event();
+    Tm = det_own.device<double>((size_t)ne.N3 * (size_t)ne.CB);      // (last: a non-null Tm says that everything above exists)
+    det_M = M;
+    return MVUS_OK;
+  }
 
   static const char* cam_kind(int k) { return k == 0 ? "alpha" : k == 1 ? "beta" : k == 2 ? "rs" : "camera parameter"; }
-  static std::string refusal(const std::string& what) {
-    return "covariance: the pivot of " + what + " is below 1e-10 of its diagonal entry of H: the normal matrix is numerically singular there -- "
+  std::string refusal(const std::string& what) const {
+    return std::string(who) + ": the pivot of " + what + " is below 1e-10 of its diagonal entry of H: the normal matrix is numerically singular there -- "
            "the gauge is probably free (settings ba_gauge: \"anchor\" / ba_freeze, mvus_ba_set_frozen)";
   }
 
   // be.x_cur holds x, the analytic Jacobian of x_cur is held, f_cur = f(x); cost = the (robust) cost at x.  Outputs are host pointers (any may be null).
   template <class SC>
-  int run(SC& sc, double cost, double sigma2_in, double* cov_cam, double* cov_band, uint8_t* estimated, CovResult& res) {
+  int run(SC& sc, double cost, double sigma2_in, double* cov_cam, double* cov_band, uint8_t* estimated, CovResult& res, const DetCovOut* det = nullptr) {
+    const std::string pre = std::string(who) + ": ";
     const auto& hp = be.hp;
     const NEView& ne = sc.ne;
     const hipStream_t st = be.stream;
     const int R = sc.BW + 1;
     // every LDS size is bounded here, from W and CB, before anything is launched
     const size_t lds_chol = (size_t)R * R * sizeof(double), lds_solve = (size_t)R * 64 * sizeof(double), lds_sel = ((size_t)R * R + R) * sizeof(double);
-    if (ne.W > kWideW || std::max(lds_chol, std::max(lds_solve, lds_sel)) > 64 * 1024) { be.err = "covariance: band wider than " + std::to_string(kWideW) + " control points"; return MVUS_E_UNSUPPORTED; }
-    if (ne.CB > 1152) { be.err = "covariance: more than 1152 camera-side unknowns"; return MVUS_E_UNSUPPORTED; }
-    if (ne.N < 1 || ne.CB < 1) { be.err = "covariance: empty problem"; return MVUS_E_INVALID; }
+    if (ne.W > kWideW || std::max(lds_chol, std::max(lds_solve, lds_sel)) > 64 * 1024) { be.err = pre + "band wider than " + std::to_string(kWideW) + " control points"; return MVUS_E_UNSUPPORTED; }
+    if (ne.CB > 1152) { be.err = pre + "more than 1152 camera-side unknowns"; return MVUS_E_UNSUPPORTED; }
+    if (ne.N < 1 || ne.CB < 1) { be.err = pre + "empty problem"; return MVUS_E_INVALID; }
     ensure(ne, sc.BW);
+    if (det) { const int rc = ensure_det(ne, hp.M); if (rc != MVUS_OK) return rc; }
     const int tot = ne.CB + ne.N3;
     mark(0);
     sc.assemble_held(be);                                    // stage 1 (the Jacobian itself was evaluated by the caller)
@@ -374,7 +416,7 @@ struct CovChain {
     }
     if (sigma2_in > 0.0) res.sigma2 = sigma2_in;
     else {
-      if (m_act <= n_est) { be.err = "covariance: " + std::to_string(m_act) + " active residual rows for " + std::to_string(n_est) + " estimated unknowns: no a-posteriori variance factor (pass sigma2)"; return MVUS_E_INVALID; }
+      if (m_act <= n_est) { be.err = pre + std::to_string(m_act) + " active residual rows for " + std::to_string(n_est) + " estimated unknowns: no a-posteriori variance factor (pass sigma2)"; return MVUS_E_INVALID; }
       res.sigma2 = 2.0 * cost / (double)(m_act - n_est);
     }
     const int m = (int)map_h.size();
@@ -414,7 +456,8 @@ struct CovChain {
     hipLaunchKernelGGL(k_cov_expand, dim3((unsigned)(((long long)ne.CB * ne.CB + 255) / 256)), dim3(256), 0, st, ne.CB, m, (const int32_t*)inv, (const double*)X, Sig);
     mark(5);
     // stage 6
-    hipLaunchKernelGGL(k_cov_tz, dim3((ne.N + kCovTP - 1) / kCovTP), dim3(256), 0, st, ne.N, ne.CB, (const double*)Z, (const double*)Sig, Rb);
+    if (det) hipLaunchKernelGGL((k_cov_tz<true, double*>), dim3((ne.N + kCovTP - 1) / kCovTP), dim3(256), 0, st, ne.N, ne.CB, (const double*)Z, (const double*)Sig, Rb, Tm);
+    else hipLaunchKernelGGL(k_cov_tz<>, dim3((ne.N + kCovTP - 1) / kCovTP), dim3(256), 0, st, ne.N, ne.CB, (const double*)Z, (const double*)Sig, Rb);
     mark(6);
     // stage 7
     hipLaunchKernelGGL(k_cov_selinv, dim3(1), dim3(256), lds_sel, st, ne.N3, sc.BW, (const double*)Lb, sel);
@@ -424,11 +467,28 @@ struct CovChain {
     hipLaunchKernelGGL(k_cov_cam_out, dim3((unsigned)(((long long)ne.CB * ne.CB + 255) / 256)), dim3(256), 0, st, hp.C, hp.P, res.sigma2, (const double*)Sig, cam_out);
     MVUS_HIP(hipGetLastError());
     mark(8);
+    // the detection pass, on request: one lane per detection, the camera in the grid's second dimension (its LDS is B x B doubles, B <= 18)
+    const bool det_run = det && hp.M > 0 && be.dp.n_chunks > 0;
+    if (det_run) {
+      int per_cam = 0;
+      for (int c = 0; c < hp.C; ++c) per_cam = std::max(per_cam, (int)(hp.cam_chunk_off[(size_t)c + 1] - hp.cam_chunk_off[(size_t)c]));
+      be.ensure_cams(be.x_cur);
+      MVUS_HIP(hipEventRecord(det_ev[0], st));
+      hipLaunchKernelGGL(k_cov_band_out, dim3((unsigned)(((long long)ne.N * 36 + 255) / 256)), dim3(256), 0, st, ne.N, ne.CB, (const uint8_t*)est, 1.0, (const double*)sel, (const double*)Rb, Gb);
+      if (per_cam > 0)
+        with_flag(hp.calib, [&](auto calib) {
+          hipLaunchKernelGGL((k_detcov<calib()>), dim3(per_cam, hp.C), dim3(kThreads), 0, st, be.dp, (const CamState*)be.cams, (const double*)be.x_cur, (const double*)be.J, (const int32_t*)be.span,
+                             ne.CB, (const double*)Sig, (const double*)Tm, (const double*)Gb, res.sigma2, det_e, det_pcov, det_t2);
+        });
+      MVUS_HIP(hipGetLastError());
+      MVUS_HIP(hipEventRecord(det_ev[1], st));
+    }
     int fl[2] = {INT_MAX, INT_MAX};
     MVUS_HIP(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, st));
     MVUS_HIP(hipStreamSynchronize(st));
     for (int s = 0; s < kCovStages; ++s) { float ms = 0.f; MVUS_HIP(hipEventElapsedTime(&ms, ev[s], ev[s + 1])); stage_ms[s] = ms; }
     timed = true;
+    if (det) { float ms = 0.f; if (det_run) MVUS_HIP(hipEventElapsedTime(&ms, det_ev[0], det_ev[1])); det_ms = ms; det_timed = true; }
     if (fl[0] >= 0 && fl[0] < ne.N3) {
       be.err = refusal("coordinate " + std::to_string(fl[0] % 3) + " of control point " + std::to_string(fl[0] / 3) + " (spline block)");
       return MVUS_E_NUMERIC;
@@ -440,6 +500,11 @@ struct CovChain {
     }
     if (cov_cam) MVUS_HIP(hipMemcpyAsync(cov_cam, cam_out, sizeof(double) * (size_t)ne.CB * ne.CB, hipMemcpyDeviceToHost, st));
     if (cov_band) MVUS_HIP(hipMemcpyAsync(cov_band, band_out, sizeof(double) * (size_t)ne.N * 36, hipMemcpyDeviceToHost, st));
+    if (det_run) {
+      if (det->e) MVUS_HIP(hipMemcpyAsync(det->e, det_e, sizeof(double) * 2 * (size_t)hp.M, hipMemcpyDeviceToHost, st));
+      if (det->pcov) MVUS_HIP(hipMemcpyAsync(det->pcov, det_pcov, sizeof(double) * 3 * (size_t)hp.M, hipMemcpyDeviceToHost, st));
+      if (det->t2) MVUS_HIP(hipMemcpyAsync(det->t2, det_t2, sizeof(double) * (size_t)hp.M, hipMemcpyDeviceToHost, st));
+    }
     MVUS_HIP(hipStreamSynchronize(st));
     return MVUS_OK;
   }

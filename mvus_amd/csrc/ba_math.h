@@ -354,6 +354,7 @@ MVUS_HD bool locate_span(const SplineView& sp, const double* x, double tau, Span
 struct ObsResult {
   double ex, ey;     // |residual| per axis (0 when not visible)
   int32_t ctrl;      // global index of the first of the 4 active control points, -1 when not visible
+  double ru, rv;     // the signed residual, predicted minus observed: ex = |ru|, ey = |rv| (k_detcov; dead in every other caller)
 };
 
 // One observation: residual and (JAC) its 2 x NS Jacobian block, rows pre-multiplied by sign(r) so
@@ -368,7 +369,7 @@ MVUS_HD ObsResult eval_observation_to(const CamState& cam, const SplineView& sp,
                                       double frame, double u_raw, double v_raw, double u_obs, double v_obs, Sink& sink) {
   const double tau = cam.alpha * (frame + cam.rs * v_raw / cam.H) + cam.beta;
   SpanLoc loc;
-  if (!locate_span(sp, x, tau, loc)) { ObsResult out; out.ex = 0.0; out.ey = 0.0; out.ctrl = -1; return out; }
+  if (!locate_span(sp, x, tau, loc)) { ObsResult out; out.ex = 0.0; out.ey = 0.0; out.ctrl = -1; out.ru = 0.0; out.rv = 0.0; return out; }
   return eval_observation_at<CALIB, JAC>(cam, tau, loc, undist, rs_free, sync_free, frame, u_raw, v_raw, u_obs, v_obs, sink);
 }
 // the same observation once its knot span is known (loc: the six knots, the twelve coefficients, the first control point)
@@ -376,7 +377,7 @@ template <bool CALIB, bool JAC, class Sink>
 MVUS_HD ObsResult eval_observation_at(const CamState& cam, double tau, const SpanLoc& loc, bool undist, bool rs_free, bool sync_free,
                                       double frame, double u_raw, double v_raw, double u_obs, double v_obs, Sink& sink) {
   ObsResult out;
-  out.ex = 0.0; out.ey = 0.0; out.ctrl = -1;
+  out.ex = 0.0; out.ey = 0.0; out.ctrl = -1; out.ru = 0.0; out.rv = 0.0;
   double h[4], dh[4];
   bspline_basis_w<JAC>(loc.tt, tau, h, dh);
   double X[3] = {0.0, 0.0, 0.0}, Xd[3] = {0.0, 0.0, 0.0};
@@ -409,6 +410,7 @@ MVUS_HD ObsResult eval_observation_at(const CamState& cam, double tau, const Spa
   }
   const double ru = uh - uo, rv = vh - vo;
   out.ex = fabs(ru); out.ey = fabs(rv);
+  out.ru = ru; out.rv = rv;
   out.ctrl = loc.ctrl;
   if (!JAC) return out;
   sink.begin(out.ctrl);

@@ -197,7 +197,7 @@ def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output
     """main.py:18-93 from the config.json at ``path`` (the reference's schema; ``create_scene``): every stage through
     ``StageTimer`` -- create_scene, cut_detection, init_alpha, time_shift, detection_to_global, init_traj(error=thres_Fmatix),
     traj_to_spline, the incremental loop, spline_to_traj; with ``settings['ba_position_priors']`` and a position log
-    (``path_position_priors``) ``Scene.align_to_position_priors`` and one final LM BA over all cameras that carries the priors; ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true; ``Scene.kinematics`` (stage 'kinematics') when
+    (``path_position_priors``) ``Scene.align_to_position_priors`` and one final LM BA over all cameras that carries the priors; ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true, ``Scene.ba_detection_covariance`` (which then serves both) when ``settings['ba_detection_covariance']`` is; ``Scene.kinematics`` (stage 'kinematics') when
     ``settings['ba_kinematics']`` is true; ``align_gt`` when the config gives ground truth; the Scene pickled to
     ``settings['path_output']`` when ``output`` and that key is set.  Returns (Scene, StageTimer)."""
     from .reconstruction import common
@@ -226,7 +226,13 @@ def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output
                   motion_weights=st['motion_weights'], rs_bounds=st['rs_bounds'])
         timer.run('spline_to_traj', num, flight.spline_to_traj, sampling_rate=1)
     flight.out = {'reconst_tran': flight.traj[1:]}
-    if flight.ba_covariance_enabled():
+    if flight.ba_detection_covariance_enabled():
+        # settings['ba_detection_covariance']: per detection the signed residual, the covariance of the fitted detection and the studentised residual,
+        # carried by the pickle as flight.detection_covariance; with settings['ba_covariance'] the same call leaves flight.covariance too
+        timer.run('ba_detection_covariance', flight.numCam, flight.ba_detection_covariance, list(flight.sequence[:flight.numCam if flight.find_order else len(flight.sequence)]),
+                  rs=st['rolling_shutter'], motion_reg=st['motion_reg'], motion_weights=st['motion_weights'], rs_bounds=st['rs_bounds'],
+                  with_covariance=flight.ba_covariance_enabled())
+    elif flight.ba_covariance_enabled():
         # settings['ba_covariance']: the covariance of the last BA's problem (all cameras of the sequence), carried by the pickle as flight.covariance
         timer.run('ba_covariance', flight.numCam, flight.ba_covariance, list(flight.sequence[:flight.numCam if flight.find_order else len(flight.sequence)]), rs=st['rolling_shutter'], motion_reg=st['motion_reg'],
                   motion_weights=st['motion_weights'], rs_bounds=st['rs_bounds'])

@@ -42,6 +42,9 @@ Extra ``settings`` keys (all optional; a reference ``config.json`` has none of t
                (``Scene.ba_frozen_mask``).
 ``ba_covariance`` True: ``mvus_amd.pipeline.reconstruct_from_config`` calls ``Scene.ba_covariance`` after the last BA and the output pickle carries
                its dict (``Scene.covariance``).  DEFAULT False: nothing changes.  Needs a fixed gauge (``ba_gauge: 'anchor'`` or ``ba_freeze``).
+``ba_detection_covariance`` True: ``reconstruct_from_config`` calls ``Scene.ba_detection_covariance`` after the last BA (one call that also yields
+               ``Scene.covariance`` when ``ba_covariance`` is on) and the output pickle carries its dict (``Scene.detection_covariance``): per
+               detection the signed residual, the 1-sigma ellipse of the fitted detection and the studentised residual.  DEFAULT False.
 ``ba_kinematics`` True: ``reconstruct_from_config`` calls ``Scene.kinematics`` after ``spline_to_traj`` (after ``Scene.ba_covariance``, with its band, when
                ``ba_covariance`` is on too) and the output pickle carries its dict.  DEFAULT False: nothing changes.
 ``ba_position_priors`` True with 'lm': ``Scene.position_priors`` -- surveyed positions (a GPS / RTK log) as a (7, K) array of t, x, y, z, sigma_x,
@@ -168,6 +171,27 @@ class Camera:
         for name in ('P', 'K', 'R', 't'):
             print('\n %s:' % name)
             print(getattr(self, name))
+
+
+def ellipse_2x2(cov):
+    """(semi_major, semi_minor, angle) of the 1-sigma ellipses of the symmetric 2 x 2 matrices cov = (uu, uv, vv), shape [3, ...]: the
+    closed form  lambda = (uu + vv) / 2 +- sqrt(((uu - vv) / 2)^2 + uv^2),  angle = atan2(2 uv, uu - vv) / 2  of the major axis from the
+    first axis towards the second, in (-pi / 2, pi / 2].  A negative small eigenvalue (rounding) gives semi_minor 0; NaN stays NaN."""
+    uu, uv, vv = (np.asarray(v, dtype=np.float64) for v in cov)
+    mean, half = 0.5 * (uu + vv), 0.5 * (uu - vv)
+    rad = np.hypot(half, uv)
+    with np.errstate(invalid='ignore'):
+        major = np.sqrt(np.maximum(mean + rad, 0.0))
+        minor = np.sqrt(np.maximum(mean - rad, 0.0))
+    return major, minor, 0.5 * np.arctan2(2.0 * uv, uu - vv)
+
+
+def chi2_2_quantile(p):
+    """The p quantile of chi^2 with 2 degrees of freedom, -2 ln(1 - p) (its distribution function is 1 - exp(-x / 2))."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError('chi2_2_quantile: p must lie in [0, 1), not %r' % (p,))
+    return -2.0 * float(np.log1p(-p))
 
 
 class Scene:
@@ -537,6 +561,7 @@ class Scene:
         self.ba_freeze()                     # (and ba_freeze / ba_gauge)
         self.ba_covariance_enabled()         # (and ba_covariance)
         self.ba_kinematics_enabled()         # (and ba_kinematics)
+        self.ba_detection_covariance_enabled()      # (and ba_detection_covariance)
         self.ba_register_enabled()           # (and ba_register / ba_register_beta_search)
         self.ba_register_beta_search()
         self.ba_position_priors()            # (and ba_position_priors / Scene.position_priors)
@@ -649,6 +674,14 @@ class Scene:
         v = st.get('ba_kinematics', False)
         if not isinstance(v, (bool, np.bool_)):
             raise ValueError("settings['ba_kinematics'] must be true or false, not %r" % (v,))
+        return bool(v)
+
+    def ba_detection_covariance_enabled(self):
+        """settings['ba_detection_covariance'] validated (a bool; absent = False): host only."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        v = st.get('ba_detection_covariance', False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("settings['ba_detection_covariance'] must be true or false, not %r" % (v,))
         return bool(v)
 
     def ba_register_enabled(self):
@@ -824,8 +857,13 @@ class Scene:
           cam_std {camera: {'alpha', 'beta', 'rs', <parameter names>}: standard deviation},
           band [N, 4, 3, 3] blocks (p, p + w) of the control points' covariance,
           t, pos_cov [len(t), 3, 3], pos_std [len(t), 3] (1-sigma per axis; NaN outside every interval)."""
-        from .. import spline as _spline
         cams = list(cams)
+        h, prob, x = self._covariance_handle(cams, rs, motion_reg, motion_weights, rs_bounds)
+        return self._store_covariance(h.covariance(x, sigma2=sigma2), cams, prob, t)
+
+    def _covariance_handle(self, cams, rs, motion_reg, motion_weights, rs_bounds):
+        """(handle, problem, x) of the covariance calls: the handle the last BA left resident when it still describes the problem over
+        ``cams`` (else a new one), with the loss, the frozen mask and the position priors of the settings in force."""
         self.alpha, self.beta, self.rs = (np.asarray(v, dtype=np.float64) for v in (self.alpha, self.beta, self.rs))
         prob = self._ba_problem(cams, rs=rs, motion_reg=motion_reg, motion_weights=motion_weights, rs_bounds=rs_bounds)
         x = self._pack(prob, cams)
@@ -838,7 +876,11 @@ class Scene:
         if not np.array_equal(mask, cur if cur is not None else np.zeros(mask.size, dtype=bool)):
             h.set_frozen(mask)
         self._apply_position_priors(h, self.ba_position_priors())
-        cv = h.covariance(x, sigma2=sigma2)
+        return h, prob, x
+
+    def _store_covariance(self, cv, cams, prob, t):
+        """``self.covariance`` from the namespace of ``BAHandle.covariance`` / ``detection_covariance`` (the dict ``ba_covariance`` documents)."""
+        from .. import spline as _spline
         C, P = len(cams), prob.P
         names = self.ba_param_names()
         sd = np.sqrt(np.diag(cv.cam))
@@ -856,6 +898,45 @@ class Scene:
                            'cam_cov': cv.cam, 'estimated_cam': cv.estimated[:C * (3 + P)].copy(), 'cam_std': cam_std, 'band': cv.band,
                            't': ts.copy(), 'pos_cov': pos_cov, 'pos_std': pos_std}
         return self.covariance
+
+    def ba_detection_covariance(self, cams, sigma2=None, rs=False, motion_reg=False, motion_weights=1, rs_bounds=False, with_covariance=False, t=None):
+        """The covariance of the BA estimate over ``cams`` carried back to the image plane (``mvus_ba_detection_covariance``), at the
+        scene's current state and built as ``ba_covariance`` is (resident handle, loss, frozen mask and priors of the settings; the gauge
+        must be fixed).  Stores (``self.detection_covariance``) and returns a data-only dict:
+          cams, sigma2, dof,
+          per_cam {camera id: {frame [M_c], e [2, M_c] signed residual (u, v) in px, predicted minus observed,
+                               cov [3, M_c] = (P_uu, P_uv, P_vv) of the fitted detection in image axes, t2 [M_c] squared studentised residual,
+                               semi_major, semi_minor [M_c] 1-sigma half axes in px, angle [M_c] of the major axis from +u towards +v (rad)}}
+        in the order of the camera's detections in the BA problem.  Detections outside every interval of the spline have NaN in cov, t2 and
+        the ellipse, 0 in e.  With ``opt_calib`` and ``undist_points`` the observed point is undistorted with the unknown intrinsics: cov is
+        then the covariance of the fitted part of the residual in the undistorted frame, not of a bare projection.  t2 is chi^2 with 2
+        degrees of freedom under the linear loss only (a robust loss: the Gauss-Newton approximation).
+        ``with_covariance``: the same call also stores ``self.covariance`` exactly as ``ba_covariance(cams, t=t, ...)`` would -- one run of
+        the chain serves both."""
+        cams = list(cams)
+        h, prob, x = self._covariance_handle(cams, rs, motion_reg, motion_weights, rs_bounds)
+        dc = h.detection_covariance(x, sigma2=sigma2)
+        if with_covariance:
+            self._store_covariance(dc, cams, prob, t)
+        off = np.asarray(prob.det_offsets, dtype=np.int64)
+        per_cam = {}
+        for k, cam in enumerate(cams):
+            seg = slice(int(off[k]), int(off[k + 1]))
+            cov = dc.cov[:, seg].copy()
+            major, minor, angle = ellipse_2x2(cov)
+            per_cam[int(cam)] = {'frame': np.array(prob.frame[seg], dtype=np.float64), 'e': dc.e[:, seg].copy(), 'cov': cov, 't2': dc.t2[seg].copy(),
+                                 'semi_major': major, 'semi_minor': minor, 'angle': angle}
+        self.detection_covariance = {'cams': [int(c) for c in cams], 'sigma2': float(dc.sigma2), 'dof': int(dc.dof), 'per_cam': per_cam}
+        return self.detection_covariance
+
+    @staticmethod
+    def studentised_flags(result, p=0.999):
+        """{camera id: bool [M_c]} of the detections whose squared studentised residual exceeds the chi^2 quantile with 2 degrees of freedom,
+        ``t2 > -2 ln(1 - p)``; NaN is never flagged.  ``result``: the dict ``ba_detection_covariance`` returned.  It only flags: nothing is
+        cut (``remove_outliers`` stays the fixed-threshold test it is)."""
+        thr = chi2_2_quantile(p)
+        with np.errstate(invalid='ignore'):
+            return {cam: np.asarray(d['t2']) > thr for cam, d in result['per_cam'].items()}
 
     FREEZE_NAMES = ('alpha', 'beta', 'rs', 'R', 't', 'K', 'd')
 
