@@ -37,6 +37,7 @@ struct mvus_ba {
   std::unique_ptr<CovChain<HipBackend>> cov;     // buffers of mvus_ba_covariance / mvus_ba_detection_covariance (ba_cov.hip.h), built on first use
   std::unique_ptr<RegisterWork> reg;             // buffers of mvus_ba_register_cameras / _linearize (ba_register.hip.h), built on first use
   mvus_rccl_handle rccl;                         // communicator of mvus_ba_set_rccl (destroyed with the handle)
+  void drop_schur() { schur.reset(); be.mem.forget_blocks(); }      // the workspace goes (it is sized by the launch tables / the time slice), and with it the blocks it held
   ~mvus_ba();
 };
 
@@ -69,12 +70,22 @@ static double time_on_stream(hipStream_t st, int warmup, int reps, F&& fn) {
   return (double)ms / reps;
 }
 
+// Who keeps what of the handle's memory (ba_held.h).  An LM solve leaves f(x), its cost and maybe the normal equations
+// for the point it returned (the carry); normal_equations and lm_step leave the blocks they assembled.  Both are valid for the very next
+// call only, unless that call's row keeps them.  The row is applied on entry, so a refused or empty call keeps what a served one keeps.
+// A new entry point picks its row here: kTransparent if it touches nothing the handle holds; kKeepsBlocks if the held Jacobian and the blocks
+// in the Schur workspace are written by HipSchur::assemble_held or not at all; else kKeepsNothing.            {carry, blocks}
+constexpr CallKeeps kTransparent{true, KeepBlocks::all};             // register_cameras, register_linearize
+constexpr CallKeeps kKeepsBlocks{false, KeepBlocks::all};            // normal_equations, lm_step, deterministic_fallback, position_prior_cost, lsmr, set_position_priors
+constexpr CallKeeps kKeepsRawBlocks{false, KeepBlocks::unfrozen};    // set_frozen: blocks with a freeze pass on them belong to the old mask
+constexpr CallKeeps kKeepsNothing{false, KeepBlocks::none};          // every other entry point: solve, covariance, detection_covariance, set_loss, ...
+
 template <class F>
-static int guarded(mvus_ba* h, F&& fn) {
+static int guarded(mvus_ba* h, CallKeeps keeps, F&& fn) {
   if (!h) return MVUS_E_INVALID;
   try {
     (void)hipSetDevice(h->be.device);
-    ++h->be.api_seq;                 // (what an LM solve carries over to the next call is valid for the very next call only: HipBackend::lm_carry)
+    h->be.mem.begin_call(keeps);
     return fn();
   } catch (const HipError& e) {
     h->be.err = e.msg;
@@ -142,11 +153,11 @@ int64_t mvus_ba_num_motion_rows(const mvus_ba* h) { return h ? h->be.hp.T : -1; 
 int32_t mvus_ba_num_slots(const mvus_ba* h) { return h ? h->be.hp.NS : -1; }
 
 int mvus_ba_set_x(mvus_ba* h, const double* x) {
-  return guarded(h, [&] { h->be.upload(h->be.x_cur, x, h->be.hp.n); return MVUS_OK; });
+  return guarded(h, kKeepsNothing, [&] { h->be.upload(h->be.x_cur, x, h->be.hp.n); return MVUS_OK; });
 }
 
 int mvus_ba_residual(mvus_ba* h, const double* x, double* f) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     be.upload(be.x_cur, x, be.hp.n);
     be.residual(be.x_cur, be.f_cur);
@@ -156,7 +167,7 @@ int mvus_ba_residual(mvus_ba* h, const double* x, double* f) {
 }
 
 int mvus_ba_residual_jacobian(mvus_ba* h, const double* x, int32_t jac_mode, double* f, double* J, int32_t* ctrl) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     be.upload(be.x_cur, x, be.hp.n);
     // rows that stay invisible are never written by the kernel: clear so the host copy is well defined
@@ -181,7 +192,7 @@ int mvus_ba_residual_jacobian(mvus_ba* h, const double* x, int32_t jac_mode, dou
 }
 
 int mvus_ba_motion_rows(mvus_ba* h, const double* x, int32_t jac_mode, double* mf, double* mJ, int32_t* mctrl) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     be.upload(be.x_cur, x, be.hp.n);
     be.jacobian(be.x_cur, be.f_cur, jac_mode);
@@ -197,7 +208,7 @@ int mvus_ba_motion_rows(mvus_ba* h, const double* x, int32_t jac_mode, double* m
 }
 
 int mvus_ba_set_pattern(mvus_ba* h, const double* x0, int32_t* pat_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     be.upload(be.x_cur, x0, be.hp.n);
     be.set_pattern(be.x_cur);
@@ -210,7 +221,7 @@ int mvus_ba_set_pattern(mvus_ba* h, const double* x0, int32_t* pat_out) {
 }
 
 int mvus_ba_upload_pattern(mvus_ba* h, const int32_t* pat, const int32_t* motion_pat) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if ((!pat && be.hp.M > 0)) { be.err = "upload_pattern: NULL pattern"; return MVUS_E_INVALID; }
     const std::string msg = be.upload_pattern(pat, motion_pat);
@@ -220,7 +231,7 @@ int mvus_ba_upload_pattern(mvus_ba* h, const int32_t* pat, const int32_t* motion
 }
 
 int mvus_ba_motion_pattern(mvus_ba* h, int32_t* motion_pat_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (be.hp.T > 0) {
       if (!motion_pat_out) { be.err = "motion_pattern: NULL output"; return MVUS_E_INVALID; }
@@ -232,19 +243,18 @@ int mvus_ba_motion_pattern(mvus_ba* h, int32_t* motion_pat_out) {
 }
 
 int mvus_ba_set_deterministic(mvus_ba* h, int32_t on) {
-  return guarded(h, [&] { h->be.det_assembly = on != 0; return MVUS_OK; });
+  return guarded(h, kKeepsNothing, [&] { h->be.det_assembly = on != 0; return MVUS_OK; });
 }
 int mvus_ba_deterministic_fallback(mvus_ba* h, int32_t* fell_back) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsBlocks, [&] {
     if (!fell_back) { h->be.err = "bad arguments"; return MVUS_E_INVALID; }
     *fell_back = (h->schur && h->schur->last_atomic) ? 1 : 0;
-    if (h->schur) h->schur->carry_held();
     return MVUS_OK;
   });
 }
 
 int mvus_ba_set_fd_groups(mvus_ba* h, const int32_t* groups, int32_t num_groups) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     if (!groups || num_groups < 1) { h->be.err = "bad arguments"; return MVUS_E_INVALID; }
     for (int64_t j = 0; j < h->be.hp.n; ++j) if (groups[j] < 0 || groups[j] >= num_groups) { h->be.err = "group index out of range"; return MVUS_E_INVALID; }
     h->be.set_fd_groups(groups, num_groups);
@@ -375,7 +385,7 @@ int32_t mvus_fd_groups(const mvus_problem* p, const int32_t* pat, const int32_t*
 }
 
 int mvus_ba_jv(mvus_ba* h, const double* v, double* y) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (!be.has_jacobian) { be.err = "no Jacobian held: call mvus_ba_residual_jacobian first"; return MVUS_E_INVALID; }
     double* vd = be.alloc(be.hp.n); double* yd = be.alloc(be.hp.m);
@@ -388,7 +398,7 @@ int mvus_ba_jv(mvus_ba* h, const double* v, double* y) {
 }
 
 int mvus_ba_jtu(mvus_ba* h, const double* u, double* z) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (!be.has_jacobian) { be.err = "no Jacobian held: call mvus_ba_residual_jacobian first"; return MVUS_E_INVALID; }
     double* ud = be.alloc(be.hp.m); double* zd = be.alloc(be.hp.n);
@@ -401,30 +411,28 @@ int mvus_ba_jtu(mvus_ba* h, const double* u, double* z) {
 }
 
 int mvus_ba_normal_equations(mvus_ba* h, double* g, double* JtJ_cam, double* band, double* cross, int32_t* W_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsBlocks, [&] {
     if (frozen_on_shards(h->be, "normal_equations") || priors_on_shards(h->be, "normal_equations")) return MVUS_E_UNSUPPORTED;
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(h->be));
-    h->schur->carry_held();
     return schur_export(h->be, *h->schur, g, JtJ_cam, band, cross, W_out);
   });
 }
 
 int mvus_ba_set_loss(mvus_ba* h, int32_t loss, double f_scale) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (loss < MVUS_LOSS_LINEAR || loss > MVUS_LOSS_ARCTAN) { be.err = "set_loss: unknown loss " + std::to_string(loss); return MVUS_E_INVALID; }
     if (!std::isfinite(f_scale) || !(f_scale > 0)) { be.err = "set_loss: f_scale must be finite and positive"; return MVUS_E_INVALID; }
-    // what an LM solve left for its point is the cost and the normal equations of the OLD loss: dropped (f(x) is evaluated again, the same
+    // what an LM solve left for its point is the cost and the normal equations of the OLD loss: not kept (f(x) is evaluated again, the same
     // bits); a changed loss is another problem, so the damping starts where a fresh handle's does
-    be.carry = LmCarry{};
-    if (loss != be.loss.kind || f_scale != be.loss.fs) { be.lm_lambda = 0; be.lm_nu = 0; }
+    if (loss != be.loss.kind || f_scale != be.loss.fs) be.mem.reset_damping();
     be.loss = LossSpec{loss, f_scale};
     return MVUS_OK;
   });
 }
 
 int mvus_ba_set_frozen(mvus_ba* h, const uint8_t* frozen, int64_t count) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsRawBlocks, [&] {
     HipBackend& be = h->be;
     const int64_t head = (int64_t)be.hp.C * (3 + be.hp.P);
     if (frozen == nullptr || count == 0) count = 0;
@@ -439,13 +447,11 @@ int mvus_ba_set_frozen(mvus_ba* h, const uint8_t* frozen, int64_t count) {
       return MVUS_E_UNSUPPORTED;
     }
     // what an LM solve left for its point -- cost, normal equations, the speculative linearisation it adopted -- belongs to the OLD set of
-    // unknowns: dropped (f(x) and the blocks are evaluated again); a changed set is another problem, so the damping starts where a fresh
-    // handle's does
-    be.carry = LmCarry{};
+    // unknowns: not kept (f(x) and the blocks are evaluated again; raw blocks of the held Jacobian stay usable); a changed set is another
+    // problem, so the damping starts where a fresh handle's does
     const std::vector<uint8_t> before = be.frozen_mask;
     be.set_frozen(frozen, count);
-    if (be.frozen_mask != before) { be.lm_lambda = 0; be.lm_nu = 0; }
-    if (h->schur) h->schur->carry_held(false);      // (raw blocks of the held Jacobian stay usable; frozen ones belong to the old mask)
+    if (be.frozen_mask != before) be.mem.reset_damping();
     return MVUS_OK;
   });
 }
@@ -453,7 +459,7 @@ int mvus_ba_set_frozen(mvus_ba* h, const uint8_t* frozen, int64_t count) {
 int64_t mvus_ba_num_frozen(const mvus_ba* h) { return h ? h->be.frozen_count : -1; }
 
 int mvus_ba_set_position_priors(mvus_ba* h, int64_t K, const double* t, const double* P, const double* w) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsBlocks, [&] {
     HipBackend& be = h->be;
     if (K < 0) { be.err = "set_position_priors: K < 0"; return MVUS_E_INVALID; }
     if (K > (1ll << 28)) { be.err = "set_position_priors: more than 2^28 priors"; return MVUS_E_INVALID; }      // (4 K and 3 K stay inside int in the kernels' indices)
@@ -469,10 +475,9 @@ int mvus_ba_set_position_priors(mvus_ba* h, int64_t K, const double* t, const do
       return MVUS_E_UNSUPPORTED;
     }
     // what an LM solve left for its point -- cost, normal equations, the speculative linearisation it adopted -- belongs to the OLD set of
-    // rows: dropped, as mvus_ba_set_loss drops it (f(x) and the blocks are evaluated again, the same bits); the damping history stays
-    be.carry = LmCarry{};
+    // rows: not kept, as with mvus_ba_set_loss (f(x) is evaluated again, the same bits; blocks of the held Jacobian stay usable: the priors'
+    // pass goes on top, HipSchur::assemble_held); the damping history stays
     be.set_priors(K, t, P, w);
-    if (h->schur) h->schur->carry_held();      // (blocks of the held Jacobian stay usable: the priors' pass goes on top, HipSchur::assemble_held)
     return MVUS_OK;
   });
 }
@@ -484,7 +489,7 @@ int64_t mvus_ba_num_position_priors(const mvus_ba* h, int64_t* active_out) {
 }
 
 int mvus_ba_position_prior_cost(mvus_ba* h, const double* x, double* cost_out, double* r_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsBlocks, [&] {
     HipBackend& be = h->be;
     if (!x || !cost_out) { be.err = "position_prior_cost: NULL argument"; return MVUS_E_INVALID; }
     if (priors_on_shards(be, "position_prior_cost")) return MVUS_E_UNSUPPORTED;
@@ -501,7 +506,6 @@ int mvus_ba_position_prior_cost(mvus_ba* h, const double* x, double* cost_out, d
     hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kThreads), 0, be.stream, pb, (const double*)be.partials, be.scal_out() + be.kPriorCostSlot);
     MVUS_HIP(hipGetLastError());
     *cost_out = 0.5 * be.read_slot(be.kPriorCostSlot);
-    if (h->schur) h->schur->carry_held();      // (nothing held was touched)
     if (r_out) {
       std::vector<double> rs((size_t)3 * K);
       be.download(rs.data(), r, 3 * K);
@@ -513,7 +517,7 @@ int mvus_ba_position_prior_cost(mvus_ba* h, const double* x, double* cost_out, d
 }
 
 int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* weights_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (!x || !cost_out) { be.err = "robust_cost: NULL argument"; return MVUS_E_INVALID; }
     if (be.allreduce || be.tshard.on) { be.err = "robust_cost: not supported on a sharded handle"; return MVUS_E_UNSUPPORTED; }
@@ -536,14 +540,13 @@ int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* w
 // mvus_ba_covariance and mvus_ba_detection_covariance: one chain (CovChain::run), the second with the detection pass behind stage 8
 static int covariance_call(mvus_ba* h, const char* who, const double* x, double sigma2, const DetCovOut* det, double* cov_cam, double* cov_band,
                            uint8_t* estimated, double* sigma2_out, int64_t* dof_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     const std::string pre = std::string(who) + ": ";
     if (!x || !std::isfinite(sigma2)) { be.err = pre + "x is NULL or sigma2 is not finite"; return MVUS_E_INVALID; }
     if (be.allreduce || be.tshard.on) { be.err = pre + "not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
-    // what an LM solve left for its point (cost, blocks, the speculative linearisation) is dropped as mvus_ba_set_loss drops it -- the blocks
+    // what an LM solve left for its point (cost, blocks, the speculative linearisation) is not kept, as with mvus_ba_set_loss -- the blocks
     // are overwritten below; the damping history stays: a later solve returns the bits it would have returned without this call
-    be.carry = LmCarry{};
     if (be.hp.C * (3 + be.hp.P) > 1152) { be.err = pre + "more than 1152 camera-side unknowns"; return MVUS_E_UNSUPPORTED; }
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
     if (!h->cov) h->cov.reset(new CovChain<HipBackend>(be));
@@ -592,7 +595,7 @@ int32_t mvus_ba_covariance_stage_ms(mvus_ba* h, double* ms_out, const char** nam
 }
 
 int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsBlocks, [&] {
     HipBackend& be = h->be;
     if (!p_out || !(lambda >= 0)) { be.err = "lm_step: bad arguments"; return MVUS_E_INVALID; }
     if (!be.has_jacobian) { be.err = "no Jacobian held: call mvus_ba_residual_jacobian first"; return MVUS_E_INVALID; }
@@ -600,7 +603,6 @@ int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
     if (be.hp.C * (3 + be.hp.P) > 1152) throw HipError{"LM_SCHUR: reduced camera system larger than 1152 unknowns"};
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
     HipSchur<HipBackend>& sc = *h->schur;
-    sc.carry_held();
     sc.assemble_held(be);
     sc.solve_async(lambda);
     be.download(p_out, sc.step_ptr(), be.hp.n);          // synchronises
@@ -612,7 +614,7 @@ int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
 
 int mvus_ba_lsmr(mvus_ba* h, const double* b, const double* D, const double* E, double damp, double atol, double btol, double conlim,
                  int64_t maxiter, double* x_out, int32_t* itn_out, int32_t* istop_out, double* norms_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsBlocks, [&] {
     HipBackend& be = h->be;
     if (!b || !x_out || !(damp >= 0)) { be.err = "lsmr: bad arguments"; return MVUS_E_INVALID; }
     if (be.allreduce || be.tshard.on) { be.err = "lsmr: not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
@@ -650,13 +652,12 @@ int mvus_ba_lsmr(mvus_ba* h, const double* b, const double* D, const double* E, 
     if (itn_out) *itn_out = itn;
     if (istop_out) *istop_out = istop;
     if (norms_out) { norms_out[0] = sc.normr; norms_out[1] = sc.normar; norms_out[2] = sc.normA; norms_out[3] = sc.condA; }
-    if (h->schur) h->schur->carry_held();      // (nothing held was touched)
     return MVUS_OK;
   });
 }
 
 int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_result* res, double* f_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (!x || !opts || !res) { be.err = "NULL argument"; return MVUS_E_INVALID; }
     const auto t0 = std::chrono::steady_clock::now();
@@ -705,7 +706,7 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
     if (opts->solver == MVUS_SOLVER_LM_SCHUR) {
       if (be.hp.C * (3 + be.hp.P) > 1152) throw HipError{"LM_SCHUR: reduced camera system larger than 1152 unknowns"};
       if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
-      so.lm_lambda0 = be.lm_lambda; so.lm_nu0 = be.lm_nu;
+      so.lm_lambda0 = be.mem.damping().lambda; so.lm_nu0 = be.mem.damping().nu;
       // knots closer than a frame (band wider than six control points): more control points than detections -- the spline is
       // held by the motion regulariser alone between the data, and a converging LM whose damping falls to 3e-3 diag(H) follows
       // noise along those directions (the incremental loop then ends 3 m off; with 0.3 it ends where TRF + LSMR ends:
@@ -713,7 +714,7 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
       constexpr double kLambdaMinWide = 0.3;
       if (h->schur->wide && so.lm_trust_radius < 0) so.lm_lambda_min = std::max(so.lm_lambda_min, kLambdaMinWide);      // (a trust region bounds those steps itself)
       sr = lm_schur(be, *h->schur, x, lb, ub, so, be.f_cur);
-      if (!sr.error) { be.lm_lambda = std::min(std::max(sr.lm_lambda, 1e-12), 1e6); be.lm_nu = std::min(sr.lm_nu, 1024.0); }
+      if (!sr.error) be.mem.store_damping(sr.lm_lambda, sr.lm_nu);
       if (sr.jac_stale) be.has_jacobian = false;      // mvus_ba_jv / jtu / lm_step must not pair J(x_old) with f(x_new)
     }
     else if (be.frozen_count > 0) {
@@ -727,7 +728,7 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
     const bool lm = opts->solver == MVUS_SOLVER_LM_SCHUR;
     if (sr.error == -4) {            // a row left the time slice: the point reached so far goes back to the caller, who re-cuts there (already in x)
       MVUS_HIP(hipStreamSynchronize(be.stream));
-      h->schur.reset();              // (the device flag is raised: the next solve on this handle starts from fresh storage)
+      h->drop_schur();               // (the device flag is raised: the next solve on this handle starts from fresh storage)
       res->cost = sr.cost; res->optimality = 0; res->nfev = sr.nfev; res->njev = sr.njev; res->status = 0; res->lin_iters = sr.lin_iters;
       res->initial_cost = sr.initial_cost; res->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       be.err = "time shard: a detection or motion row reaches control points outside this rank's slice +- halo (the time stamps have drifted since the cuts were made): re-cut at the returned point";
@@ -758,11 +759,8 @@ static int register_call(mvus_ba* h, const char* who, const double* x, int32_t B
   }
   if (B == 0) return MVUS_OK;                    // nothing to do: no state is looked at
   if (!h) { g_create_error = std::string(who) + ": NULL handle"; return MVUS_E_INVALID; }
-  return guarded(h, [&] {
+  return guarded(h, kTransparent, [&] {      // nothing the handle holds is touched: what an LM solve left for the very next call stays valid for the call after this one
     HipBackend& be = h->be;
-    // nothing the handle holds is touched: what an LM solve left for the very next call stays valid for the call after this one
-    if (be.carry_seq + 1 == be.api_seq) be.carry_seq = be.api_seq;
-    if (h->schur) h->schur->carry_held();
     if (reg_check_batch(who, be.hp.C, be.hp.P, B, cam, start, msg, sizeof msg)) { be.err = msg; return MVUS_E_INVALID; }
     if (!x) { be.err = std::string(who) + ": x is NULL"; return MVUS_E_INVALID; }
     if (be.allreduce || be.tshard.on) { be.err = std::string(who) + ": not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
@@ -788,7 +786,7 @@ int mvus_ba_register_linearize(mvus_ba* h, const double* x, int32_t B, const int
 }
 
 int mvus_ba_outlier_mask(mvus_ba* h, const double* x, double thres, uint8_t* keep) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     be.upload(be.x_cur, x, be.hp.n);
     be.residual(be.x_cur, be.f_cur);
@@ -802,10 +800,10 @@ int mvus_ba_outlier_mask(mvus_ba* h, const double* x, double thres, uint8_t* kee
 }
 
 int mvus_ba_remove_outliers(mvus_ba* h, const double* x, double thres, uint8_t* keep_out, int64_t* det_offsets_out) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     be.upload(be.x_cur, x, be.hp.n);
-    h->schur.reset();                       // sized by the launch tables
+    h->drop_schur();                        // sized by the launch tables
     be.remove_outliers(be.x_cur, thres, keep_out, det_offsets_out);
     if (be.allreduce) be.reduce_row_count();
     return MVUS_OK;
@@ -848,7 +846,7 @@ static int rccl_allreduce_cb(void* user, void* buf, size_t count, void* stream) 
 }
 
 int mvus_ba_set_allreduce(mvus_ba* h, mvus_allreduce_fn fn, void* user, int32_t is_root) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (fn != rccl_allreduce_cb && h->rccl.comm) {      // another route (or none) replaces the library's own communicator: tear it down
       MVUS_HIP(hipStreamSynchronize(be.stream));
@@ -889,7 +887,7 @@ int mvus_rccl_unique_id(uint8_t id_out[128]) {
 }
 
 int mvus_ba_set_rccl(mvus_ba* h, const uint8_t id[128], int32_t rank, int32_t world, int32_t is_root) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (!id || world < 1 || rank < 0 || rank >= world) { be.err = "set_rccl: bad arguments"; return MVUS_E_INVALID; }
     {
@@ -910,7 +908,7 @@ int mvus_ba_set_rccl(mvus_ba* h, const uint8_t id[128], int32_t rank, int32_t wo
 }
 
 int mvus_ba_time_allreduce(mvus_ba* h, int64_t count, int32_t reps, double* avg_ms) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (count < 1 || reps < 1 || !avg_ms) { be.err = "bad arguments"; return MVUS_E_INVALID; }
     if (!be.allreduce) { be.err = "time_allreduce: no all-reduce route installed"; return MVUS_E_INVALID; }
@@ -923,13 +921,13 @@ int mvus_ba_time_allreduce(mvus_ba* h, int64_t count, int32_t reps, double* avg_
 }
 
 int mvus_ba_set_time_shard(mvus_ba* h, int32_t rank, int32_t world, const int32_t* ctrl_cuts, int32_t halo) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (world < 1 || rank < 0 || rank >= world || !ctrl_cuts || halo < 1) { be.err = "set_time_shard: bad arguments"; return MVUS_E_INVALID; }
     if (ctrl_cuts[0] != 0 || ctrl_cuts[world] != be.hp.N) { be.err = "set_time_shard: cuts must run from 0 to the number of control points"; return MVUS_E_INVALID; }
     for (int r = 0; r < world; ++r)
       if (ctrl_cuts[r + 1] <= ctrl_cuts[r]) { be.err = "set_time_shard: cuts must increase"; return MVUS_E_INVALID; }
-    h->schur.reset();
+    h->drop_schur();
     be.tshard.on = world > 1; be.tshard.rank = rank; be.tshard.world = world; be.tshard.halo = halo;
     be.tshard.cuts.assign(ctrl_cuts, ctrl_cuts + world + 1);
     be.dp.mot_lo = be.tshard.on ? ctrl_cuts[rank] : 0;
@@ -940,7 +938,7 @@ int mvus_ba_set_time_shard(mvus_ba* h, int32_t rank, int32_t world, const int32_
 }
 
 int mvus_ba_time_kernel(mvus_ba* h, int32_t which, int32_t launches, double* avg_ms) {
-  return guarded(h, [&] {
+  return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
     if (launches < 1 || !avg_ms || which < 0 || which > 6) { be.err = "bad arguments"; return MVUS_E_INVALID; }
     be.ensure_J();

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "ba_held.h"
 #include "ba_kernels.hip.h"
 #include "ba_problem.h"
 #include "ba_solver.h"
@@ -84,7 +85,7 @@ struct HipBackend {
   // time shard (mvus_ba_set_time_shard): this handle holds the detections of one time slice and owns the control points
   // cuts[rank] .. cuts[rank+1]; the LM/Schur path then keeps the spline blocks of that slice (+- halo) only
   struct TimeShard { bool on = false; int rank = 0, world = 1, halo = 8; std::vector<int> cuts; } tshard;
-  double lm_lambda = 0, lm_nu = 0;   // LM damping and its growth factor, carried from one solve on this handle to the next
+  HandleMemory mem;                  // what the handle remembers from one API call to the next (ba_held.h): resume point, carry, damping, blocks' token
   // MVUS_JAC_FD
   int32_t* fd_groups = nullptr;
   int fd_ngroups = 0;
@@ -276,47 +277,14 @@ struct HipBackend {
   double* tr_pn2 = nullptr;         // |p|^2 of the damped step (trust region of the LM driver)
   bool reshard_flag = false;        // set by HipSchur::solve_ok when a row left the time slice
   bool reshard_pending() { const bool r = reshard_flag; reshard_flag = false; return r; }
-  // current / trial point of the LM driver, kept from solve to solve (ba_schur.h: lm_resume)
+  // current / trial point of the LM driver, kept from solve to solve; which of the two holds the point the last solve returned, and
+  // what that solve left valid there, is the handle's memory (ba_held.h) -- the driver's names for it (ba_schur.h):
   double* lm_x[2] = {nullptr, nullptr};
-  std::vector<double> lm_last_host;
-  const double* lm_last_ptr = nullptr;   // host copy of the point the last solve returned: the pinned mirror the trial kernel wrote (no copy), else lm_last_host
-  int lm_last = -1;
   double* lm_xbuf(int k) { if (!lm_x[k]) lm_x[k] = dalloc<double>(std::max<int64_t>(hp.n, 1)); return lm_x[k]; }
-  // Consulting the remembered point DISARMS it: from here on the solve writes into both buffers (upload, trial points), so only a solve
-  // that reaches lm_remember -- a normal or a reshard exit -- re-arms it.  A solve that leaves early (non-finite cost at x0, an exception)
-  // therefore cannot leave a stale "buffer k holds the point I returned" behind for a caller that retries from the last good point.
-  int lm_resume(const double* x_host) {
-    int r = -1;
-    if (lm_last >= 0 && lm_last_ptr != nullptr && !allreduce && std::memcmp(lm_last_ptr, x_host, sizeof(double) * hp.n) == 0) r = lm_last;
-    lm_last = -1; lm_last_ptr = nullptr;
-    return r;
-  }
-  // mirror: the pinned host buffer that holds the returned point already (written by the accepted trial's kernel).  Every solve starts its
-  // trials at mirror 0 again: the comparison in lm_resume happens before any trial of that solve is launched, and a resumed solve that
-  // accepts no step re-remembers through the caller's x (mirror == nullptr) -- else the point is copied
-  void lm_remember(const double* x_dev, const double* x_host, const double* mirror) {
-    lm_last = x_dev == lm_x[0] ? 0 : (x_dev == lm_x[1] ? 1 : -1);
-    lm_last_ptr = nullptr;
-    if (lm_last < 0) return;
-    if (mirror != nullptr) lm_last_ptr = mirror;
-    else { lm_last_host.assign(x_host, x_host + hp.n); lm_last_ptr = lm_last_host.data(); }
-  }
-  // What the last LM solve left for the point it returned (ba_schur.h: LmCarry).  Valid for the NEXT call on the handle only: every entry
-  // point bumps api_seq (guarded), so any call in between -- a residual, a pattern, an outlier removal -- disarms it; consulting it
-  // disarms it as well (a solve that fails early must not leave it behind).
-  uint64_t api_seq = 0, carry_seq = 0;
-  LmCarry carry{};
-  int carry_jac_mode = -1;
-  LmCarry lm_carry(int jac_mode) {
-    LmCarry c{};
-    if (carry.f_valid && carry_seq + 1 == api_seq && !allreduce && !sw.lm_no_carry) {
-      c = carry;
-      if (carry_jac_mode != jac_mode) c.lin_valid = false;
-    }
-    carry = LmCarry{};
-    return c;
-  }
-  void lm_keep(const LmCarry& c, int jac_mode) { carry = c; carry_seq = api_seq; carry_jac_mode = jac_mode; }
+  int lm_resume(const double* x_host) { return mem.resume(x_host, hp.n, !allreduce); }
+  void lm_remember(const double* x_dev, const double* x_host, const double* mirror) { mem.remember(x_dev == lm_x[0] ? 0 : (x_dev == lm_x[1] ? 1 : -1), x_host, hp.n, mirror); }
+  LmCarry lm_carry(int jac_mode) { return mem.take_carry(jac_mode, !allreduce && !sw.lm_no_carry); }
+  void lm_keep(const LmCarry& c, int jac_mode) { mem.keep_carry(c, jac_mode); }
   // fetch_mark: the next fetch waits for the work enqueued so far only (an event), not for what is enqueued after the mark -- the
   // speculative linearisation of the LM driver.  Needs the scalars written straight into mapped memory (one rank).
   // fetch_poll_begin: the same without an event (hipEventRecord costs a 6 us bubble between the two kernels it separates): the FIRST

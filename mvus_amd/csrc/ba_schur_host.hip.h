@@ -584,33 +584,27 @@ struct HipSchur {
 
   // normal equations of the Jacobian the backend holds: the analytic Jacobian of x_cur goes through the fused window-major assembly
   // (the LM path's kernel; MVUS_NE_FROM_J=1 forms them from the stored blocks instead), anything else is assembled from J
-  // With a mask in force the blocks of the held Jacobian are assembled ONCE: if the call before this one on the handle left them here
-  // (held_seq, carried over mvus_ba_normal_equations / lm_step / set_frozen / deterministic_fallback only -- any other entry point
-  // lets it lapse), the masked system is those blocks with the freeze pass applied, entry for entry -- also behind the detection-major
-  // kernel, whose atomics would give a second assembly other last bits.  A handle without a mask assembles on every call, as always.
-  // Position priors (mvus_ba_set_position_priors) the same way: blocks the call before left here WITHOUT priors receive the priors' pass on
-  // top, blocks that carry the priors in force already (held_prior_gen) are used as they are -- the difference between the exported
-  // blocks with and without priors is then the priors' contribution entry for entry on the detection-major route as well; blocks that
-  // carry OTHER priors are assembled again.  A handle with neither a mask nor active priors assembles on every call, as always.
-  uint64_t held_seq = 0, held_prior_gen = 0;
-  bool held_frozen = false, held_fused = false;
-  void carry_held(bool keep_frozen = true) { if (held_seq != 0 && held_seq + 1 == be.api_seq && (keep_frozen || !held_frozen)) held_seq = be.api_seq; }
+  // Under a mask or position priors the blocks the call before this one left here are used again, with the missing passes on top, where
+  // the handle's memory says they may be (HandleMemory::blocks_reusable, ba_held.h; which entry points keep them: the table of ba_api.hip)
+  // -- the masked system is then the raw blocks with the freeze pass applied, the difference between the exported blocks with and without
+  // priors the priors' contribution, entry for entry, also behind the detection-major kernel, whose atomics would give a second assembly
+  // other last bits.  A handle with neither a mask nor active priors assembles on every call, as always.
   void assemble_held(BE&) {
     const bool fused = be.held_analytic_at_xcur && use_win && !sw.ne_from_j;
-    const uint64_t pg = be.prior_active > 0 ? be.prior_gen : 0;
-    if ((be.frozen_count > 0 || pg != 0) && held_seq == be.api_seq && held_fused == fused && (held_prior_gen == 0 || held_prior_gen == pg) &&
-        (!held_frozen || be.frozen_count > 0)) {
-      if (held_prior_gen == 0 && pg != 0) {
+    const BlocksTag want{be.frozen_count > 0, fused, be.prior_active > 0 ? be.prior_gen : 0};
+    if (be.mem.blocks_reusable(want)) {
+      const BlocksTag& held = be.mem.held_blocks();
+      if (held.prior_gen == 0 && want.prior_gen != 0) {
         be.prior_normal_equations(ne, fused ? be.x_cur : be.jac_x);
         diag_pending = true;
       }
-      if (!held_frozen && be.frozen_count > 0) {
+      if (!held.frozen && want.frozen) {
         hipLaunchKernelGGL(k_freeze_ne, dim3((unsigned)be.frozen_count), dim3(kFreezeThreads), 0, be.stream, ne, (const int32_t*)be.frozen_idx, be.frozen_count);
         MVUS_HIP(hipGetLastError());
         diag_pending = true;
       }
     } else assemble(be, be.f_cur, fused ? be.x_cur : nullptr, fused ? be.span : nullptr);
-    held_seq = be.api_seq; held_frozen = be.frozen_count > 0; held_fused = fused; held_prior_gen = pg;
+    be.mem.stamp_blocks(want);
   }
 
   void flush_diag() {

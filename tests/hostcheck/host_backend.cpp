@@ -13,6 +13,7 @@
 
 #include "../../mvus_amd/csrc/ba_problem.h"
 #include "../../mvus_amd/csrc/ba_solver.h"
+#include "../../mvus_amd/csrc/ba_held.h"
 #ifdef MVUS_WITH_SCHUR
 #include "../../mvus_amd/csrc/ba_schur.h"
 #endif
@@ -71,11 +72,15 @@ struct HostBackend {
   static constexpr bool kDeviceLsmr = false;
   std::vector<double> lm_x[2];
   double* lm_xbuf(int k) { lm_x[k].resize((size_t)hp.n); return lm_x[k].data(); }
-  int lm_resume(const double*) { return -1; }
+  // the record the library's handle keeps between calls (ba_held.h); null: a handle without memory -- every solve starts from scratch
+  mvus::HandleMemory* mem = nullptr;
+  int lm_resume(const double* x) { return mem ? mem->resume(x, hp.n, true) : -1; }
   bool reshard_pending() { return false; }
-  void lm_remember(const double*, const double*, const double*) {}
-  mvus::LmCarry lm_carry(int) { return {}; }
-  void lm_keep(const mvus::LmCarry&, int) {}
+  void lm_remember(const double* x_dev, const double* x_host, const double* mirror) {
+    if (mem) mem->remember(x_dev == lm_x[0].data() ? 0 : (x_dev == lm_x[1].data() ? 1 : -1), x_host, hp.n, mirror);
+  }
+  mvus::LmCarry lm_carry(int jac_mode) { return mem ? mem->take_carry(jac_mode, true) : mvus::LmCarry{}; }
+  void lm_keep(const mvus::LmCarry& c, int jac_mode) { if (mem) mem->keep_carry(c, jac_mode); }
   void fetch_mark() {}
   void fetch_enqueue(const double*, int) {}
   double* mirror_dev(int) { return nullptr; }
@@ -136,8 +141,10 @@ struct HostBackend {
       }
     }
   }
-  void residual(const double* x, double* f) { eval<false>(x, f, 0); }
+  int64_t n_residual = 0, n_jacobian = 0;      // calls of the two below since the handle was made (hostcheck_lm_chain reports them per solve)
+  void residual(const double* x, double* f) { ++n_residual; eval<false>(x, f, 0); }
   void jacobian(const double* x, double* f, int jac_mode) {
+    ++n_jacobian;
     if (jac_mode == MVUS_JAC_FD) jacobian_fd(x, f); else eval<true>(x, f, jac_mode);
   }
   void jacobian_fd(const double* x, double* f) {
@@ -409,6 +416,73 @@ int hostcheck_solve(void* h, double* x, const mvus_solve_opts* o, mvus_result* r
   r->cost = sr.cost; r->optimality = sr.optimality; r->nfev = sr.nfev; r->njev = sr.njev; r->status = sr.status;
   r->lin_iters = sr.lin_iters; r->initial_cost = sr.initial_cost; r->solve_ms = 0;
   return 0;
+}
+
+#ifdef MVUS_WITH_SCHUR
+// A chain of lm_schur solves on one handle, run the way mvus_ba_solve runs them: one residual buffer and one HostSchur for the whole chain,
+// every solve from the point the one before returned, with its own budget (budgets[k] = max_nfev), the damping handed on.  rows[k] stands for
+// an API call between solve k - 1 and solve k, by its table row alone (begin_call): -1 none, else keeps_carry + 2 * KeepBlocks.  poison[k]:
+// solve k is handed a NaN in x[0] -- it refuses (status[k] = the driver's error), and the chain goes on from the last good point.
+// memory == 0: the backend has no HandleMemory.  Per solve: x (n values), cost, nfev, njev, status, jac_stale and the backend's evaluations it took.
+int hostcheck_lm_chain(void* h, const double* x0, const mvus_solve_opts* o, int nsolve, const int32_t* budgets, const int32_t* rows, const uint8_t* poison,
+                       int memory, double* x_out, double* cost, int32_t* nfev, int32_t* njev, int32_t* status, int32_t* jac_stale, int64_t* n_residual, int64_t* n_jacobian) {
+  HostBackend* be = static_cast<HostBackend*>(h);
+  const int64_t n = be->hp.n;
+  std::vector<double> x(x0, x0 + n), lb(n, -INFINITY), ub(n, INFINITY), f(be->hp.m);
+  if (be->hp.rs_bounds) for (int c = 0; c < be->hp.C; ++c) { lb[2 * be->hp.C + c] = 0.0; ub[2 * be->hp.C + c] = 1.0; }
+  SolveOptions so;
+  so.jac_mode = o->jac_mode; so.ftol = o->ftol; so.xtol = o->xtol; so.gtol = o->gtol; so.verbose = o->verbose;
+  so.lm_lambda_min = o->lm_lambda_min; so.lm_trust_radius = o->lm_trust_radius;
+  HandleMemory mem;
+  HostSchur sc;
+  be->mem = memory ? &mem : nullptr;
+  for (int k = 0; k < nsolve; ++k) {
+    if (rows[k] >= 0) mem.begin_call(CallKeeps{(rows[k] & 1) != 0, static_cast<KeepBlocks>(rows[k] >> 1)});
+    mem.begin_call(CallKeeps{false, KeepBlocks::none});      // mvus_ba_solve's row
+    so.max_nfev = budgets[k]; so.lm_lambda0 = mem.damping().lambda; so.lm_nu0 = mem.damping().nu;
+    std::vector<double> xs(x);
+    if (poison[k]) xs[0] = NAN;
+    const int64_t r0 = be->n_residual, j0 = be->n_jacobian;
+    const SolveResult sr = lm_schur(*be, sc, xs.data(), lb, ub, so, f.data());
+    if (!sr.error) { mem.store_damping(sr.lm_lambda, sr.lm_nu); x = xs; }
+    std::memcpy(x_out + (size_t)k * n, x.data(), sizeof(double) * n);
+    cost[k] = sr.cost; nfev[k] = sr.nfev; njev[k] = sr.njev; status[k] = sr.error ? sr.error : sr.status;
+    jac_stale[k] = sr.jac_stale ? 1 : 0;      // (the blocks the Schur object holds are an earlier point's: the solve ended on its budget with an accepted step)
+    n_residual[k] = be->n_residual - r0; n_jacobian[k] = be->n_jacobian - j0;
+  }
+  be->mem = nullptr;
+  return 0;
+}
+#endif
+
+// a bare HandleMemory (ba_held.h), driven call by call
+void* hostcheck_mem_new() { return new HandleMemory(); }
+void hostcheck_mem_free(void* m) { delete static_cast<HandleMemory*>(m); }
+void hostcheck_mem_begin_call(void* m, int keeps_carry, int keep_blocks) {
+  static_cast<HandleMemory*>(m)->begin_call(CallKeeps{keeps_carry != 0, static_cast<KeepBlocks>(keep_blocks)});
+}
+int hostcheck_mem_resume(void* m, const double* x, int64_t n, int usable) { return static_cast<HandleMemory*>(m)->resume(x, n, usable != 0); }
+void hostcheck_mem_remember(void* m, int slot, const double* x, int64_t n, const double* mirror) { static_cast<HandleMemory*>(m)->remember(slot, x, n, mirror); }
+int hostcheck_mem_take_carry(void* m, int jac_mode, int usable, double* cost_out) {      // f_valid + 2 * lin_valid
+  const LmCarry c = static_cast<HandleMemory*>(m)->take_carry(jac_mode, usable != 0);
+  if (cost_out) *cost_out = c.cost;
+  return (c.f_valid ? 1 : 0) + (c.lin_valid ? 2 : 0);
+}
+void hostcheck_mem_keep_carry(void* m, int f_valid, int lin_valid, double cost, int jac_mode) {
+  static_cast<HandleMemory*>(m)->keep_carry(LmCarry{f_valid != 0, lin_valid != 0, cost}, jac_mode);
+}
+void hostcheck_mem_damping(void* m, int op, double lambda, double nu, double* out) {      // op 1: store, 2: reset; out[2]: the damping afterwards
+  HandleMemory* hm = static_cast<HandleMemory*>(m);
+  if (op == 1) hm->store_damping(lambda, nu);
+  if (op == 2) hm->reset_damping();
+  out[0] = hm->damping().lambda; out[1] = hm->damping().nu;
+}
+int hostcheck_mem_blocks(void* m, int op, int frozen, int fused, uint64_t prior_gen) {      // op 0: reusable for this tag?  1: stamp, 2: forget
+  HandleMemory* hm = static_cast<HandleMemory*>(m);
+  const BlocksTag tag{frozen != 0, fused != 0, prior_gen};
+  if (op == 1) hm->stamp_blocks(tag);
+  if (op == 2) hm->forget_blocks();
+  return op == 0 ? (hm->blocks_reusable(tag) ? 1 : 0) : 0;
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ from mvus_amd import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = [os.path.join(HERE, 'hostcheck', f) for f in ('hostcheck.cpp', 'host_backend.cpp')]
-DEPS = SRC + [os.path.join(ROOT, 'mvus_amd', 'csrc', f) for f in ('ba_math.h', 'ba_switches.h', 'ba_solver.h', 'ba_problem.h', 'ba_schur.h', 'ba_partition.h', 'triangulate.hip.h', 'spline_fit.hip.h', 'pnp.hip.h', 'epipolar.hip.h')] \
+DEPS = SRC + [os.path.join(ROOT, 'mvus_amd', 'csrc', f) for f in ('ba_math.h', 'ba_switches.h', 'ba_solver.h', 'ba_held.h', 'ba_problem.h', 'ba_schur.h', 'ba_partition.h', 'triangulate.hip.h', 'spline_fit.hip.h', 'pnp.hip.h', 'epipolar.hip.h')] \
     + [os.path.join(ROOT, 'include', 'mvus_ba.h')]
 SO = os.path.join(HERE, 'hostcheck', 'libhostcheck.so')
 
@@ -46,6 +46,20 @@ def load():
         + [ctypes.c_int64, _lib.c_double_p, _lib.c_int32_p, _lib.c_int32_p, _lib.c_double_p]
     lib.hostcheck_solve.argtypes = [ctypes.c_void_p, _lib.c_double_p, ctypes.POINTER(_lib.MvusSolveOpts),
                                     ctypes.POINTER(_lib.MvusResult), _lib.c_double_p]
+    lib.hostcheck_lm_chain.argtypes = [ctypes.c_void_p, _lib.c_double_p, ctypes.POINTER(_lib.MvusSolveOpts), ctypes.c_int, _lib.c_int32_p, _lib.c_int32_p,
+                                       _lib.c_uint8_p, ctypes.c_int, _lib.c_double_p, _lib.c_double_p, _lib.c_int32_p, _lib.c_int32_p, _lib.c_int32_p,
+                                       _lib.c_int32_p, _lib.c_int64_p, _lib.c_int64_p]
+    lib.hostcheck_mem_new.restype = ctypes.c_void_p
+    lib.hostcheck_mem_free.restype = lib.hostcheck_mem_begin_call.restype = lib.hostcheck_mem_remember.restype = None
+    lib.hostcheck_mem_keep_carry.restype = lib.hostcheck_mem_damping.restype = None
+    lib.hostcheck_mem_free.argtypes = [ctypes.c_void_p]
+    lib.hostcheck_mem_begin_call.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+    lib.hostcheck_mem_resume.argtypes = [ctypes.c_void_p, _lib.c_double_p, ctypes.c_int64, ctypes.c_int]
+    lib.hostcheck_mem_remember.argtypes = [ctypes.c_void_p, ctypes.c_int, _lib.c_double_p, ctypes.c_int64, _lib.c_double_p]
+    lib.hostcheck_mem_take_carry.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _lib.c_double_p]
+    lib.hostcheck_mem_keep_carry.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int]
+    lib.hostcheck_mem_damping.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, _lib.c_double_p]
+    lib.hostcheck_mem_blocks.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64]
     lib.hostcheck_triangulate.argtypes = [ctypes.c_longlong] + [_lib.c_double_p] * 7
     lib.hostcheck_fpdisc.argtypes = [ctypes.c_int, _lib.c_double_p, _lib.c_double_p]
     lib.hostcheck_fprati.restype = ctypes.c_double
@@ -195,6 +209,27 @@ class HostHandle:
         if rc != 0:
             raise ValueError(self.lib.hostcheck_error().decode())
         return x, res, f
+
+    def lm_chain(self, x0, opts, budgets, memory, rows=None, poison=None):
+        """A chain of host LM solves on one handle, each from the point the one before returned (hostcheck_lm_chain).  rows[k]: the table
+        row (keeps_carry + 2 * KeepBlocks) of an API call in front of solve k, -1 none; poison[k]: solve k is handed a NaN.  Returns one
+        SimpleNamespace per solve: x, cost, nfev, njev, status, jac_stale, n_residual, n_jacobian."""
+        from types import SimpleNamespace
+        K = len(budgets)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        b = np.ascontiguousarray(budgets, dtype=np.int32)
+        r = np.ascontiguousarray(rows if rows is not None else [-1] * K, dtype=np.int32)
+        p = np.ascontiguousarray(poison if poison is not None else [0] * K, dtype=np.uint8)
+        assert b.shape == r.shape == p.shape == (K,)
+        x, cost = np.zeros((K, self.n)), np.zeros(K)
+        nfev, njev, status, stale = (np.zeros(K, dtype=np.int32) for _ in range(4))
+        nres, njac = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+        i32 = lambda a: a.ctypes.data_as(_lib.c_int32_p)
+        i64 = lambda a: a.ctypes.data_as(_lib.c_int64_p)
+        self.lib.hostcheck_lm_chain(self.h, _lib.dptr(x0), ctypes.byref(opts), K, i32(b), i32(r), p.ctypes.data_as(_lib.c_uint8_p), int(bool(memory)),
+                                    _lib.dptr(x), _lib.dptr(cost), i32(nfev), i32(njev), i32(status), i32(stale), i64(nres), i64(njac))
+        return [SimpleNamespace(x=x[k], cost=cost[k], nfev=int(nfev[k]), njev=int(njev[k]), status=int(status[k]), jac_stale=bool(stale[k]),
+                                n_residual=int(nres[k]), n_jacobian=int(njac[k])) for k in range(K)]
 
 
 def host_triangulate(x1, x2, P1, P2, errors=True):
