@@ -37,31 +37,33 @@ struct Switches {
   bool lsmr_trace = false;
 
   // ---- HipSchur (ba_schur_host.hip.h) ----
-  // MVUS_GEMM_SLABS=k (k > 0): K-slabs of the Schur product.  Default 0 = the cost model of plan_gemm.  test_gpu_schur.py.
+  // MVUS_GEMM_SLABS=k (k > 0): K-slabs of the Schur product.  Default 0 = the cost model of plan_gemm.  test_gpu_schur.py,
+  // test_gpu_schur_backward_error.py.
   int gemm_slabs = 0;
   // MVUS_RCS=gj: the reduced camera system by the block Gauss-Jordan (k_schur_finish, k_gj_step) instead of the blocked L D L^T.
-  // Default off.  test_gpu_rcs.py.
+  // Default off.  test_gpu_rcs.py, test_gpu_schur_backward_error.py.
   bool rcs_gj = false;
   // MVUS_RCS_TRSM=launch: the rows below a super-block in a launch of their own (k_rcs_trsm) instead of inside k_rcs_factor.
-  // Default off.  test_gpu_rcs.py.
+  // Default off.  test_gpu_rcs.py, test_gpu_schur_backward_error.py.
   bool rcs_trsm_launch = false;
   // MVUS_RCS_SPIN_LIMIT=n: polls before a waiting workgroup of k_rcs_factor / k_sep_bcr_levels gives up; 0 = the first poll that finds
   // the flag behind.  Default -1 = unset (kRcsSpinLimit).  Test hook: test_gpu_rcs.py, test_gpu_schur.py.
   long long rcs_spin_limit = -1;
-  // MVUS_BCR_FUSED=0: a launch per wide cyclic-reduction level instead of one for all (k_sep_bcr_levels).  Default on.  test_gpu_schur.py.
+  // MVUS_BCR_FUSED=0: a launch per wide cyclic-reduction level instead of one for all (k_sep_bcr_levels).  Default on.  test_gpu_schur.py,
+  // test_gpu_schur_backward_error.py.
   bool bcr_fused = true;
   // MVUS_PART_LEN=n: control points per interior of the band solver.  Clamped to [two separators, kPartL].  Default 0 = unset (kPartL, half
   // of it up to 128 camera unknowns).
-  // test_gpu_rcs.py.
+  // test_gpu_rcs.py, test_gpu_schur_backward_error.py (16, 32, and 6 = the longest separator chain a spline can have).
   int part_len = 0;
   // MVUS_PART_BACK (set): the interiors' columns are back-corrected (k_part_back) and the Schur product carries no correction rows.
-  // Default off.  test_gpu_rcs.py.
+  // Default off.  test_gpu_rcs.py, test_gpu_schur_backward_error.py.
   bool part_back = false;
   // MVUS_DIRECT_RHS=0: the right-hand-side copy Z = E is made instead of the interior solves reading the assembled blocks.
-  // Default on.  test_gpu_rcs.py.
+  // Default on.  test_gpu_rcs.py, test_gpu_schur_backward_error.py.
   bool direct_rhs = true;
   // MVUS_SEP_SEQUENTIAL (set): the sequential block-tridiagonal separator kernels instead of the cyclic reduction.  Default off.
-  // test_gpu_schur.py.
+  // test_gpu_schur.py, test_gpu_schur_backward_error.py.
   bool sep_sequential = false;
   // MVUS_SEP_TWO_LEVEL=0: time shards sum the whole separator system instead of the cut separators only.  Default on.  test_gpu_dist.py.
   bool sep_two_level = true;
@@ -82,7 +84,7 @@ struct Switches {
   // Default off.  test_gpu_det_assembly.py, test_gpu_frozen.py, test_gpu_jacobian_exact.py, test_gpu_robust_loss.py.
   bool ne_from_j = false;
   // MVUS_NO_OVERLAP (set): the interiors are not factorised beside the right-hand-side copies (k_build_rhs + k_part_cholesky).
-  // Default off.  A/B by hand.
+  // Default off.  test_gpu_schur_backward_error.py.
   bool no_overlap = false;
   // MVUS_DEBUG (set): one line on stderr for the window plan, a failed solve and a hand-over time-out.  Default off.
   // test_gpu_rcs.py, test_gpu_schur.py (they count the time-out lines).

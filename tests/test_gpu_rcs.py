@@ -10,32 +10,18 @@ of round 5 (no right-hand-side copy, no back-correction) against the path time s
 import numpy as np
 import pytest
 
+from lm_reference import assert_backward_error, route_factor
 from mvus_amd import _lib
 from mvus_amd import problem as mp
+from schur_reference import dense
 
 pytestmark = pytest.mark.gpu
 
 
 def _dense_step(prob, h, lam):
     """(H + lam diag H) p = -g with H, g from mvus_ba_normal_equations, solved densely on the host."""
-    from test_gpu_schur import internal_index
     g, A, band, cross = h.normal_equations()
-    n, C, B, W = prob.n_params, prob.C, 3 + prob.P, band.shape[1]
-    N = int(prob.n_coef.sum())
-    cam_idx, spl_idx = internal_index(prob)
-    H = np.zeros((n, n))
-    for c in range(C):
-        H[np.ix_(cam_idx[c], cam_idx[c])] = A[c]
-    E = cross.reshape(C * B, 3 * N)
-    ci = cam_idx.ravel()
-    H[np.ix_(ci, spl_idx)] = E
-    H[np.ix_(spl_idx, ci)] = E.T
-    for w in range(W):
-        for gi in range(N - w):
-            ri, cj = spl_idx[3 * gi:3 * gi + 3], spl_idx[3 * (gi + w):3 * (gi + w) + 3]
-            H[np.ix_(ri, cj)] = band[gi, w]
-            if w > 0:
-                H[np.ix_(cj, ri)] = band[gi, w].T
+    H = dense(prob, g, A, band, cross)
     d = np.diag(H).copy()
     d = np.where(d > 0, d, 1.0)
     return np.linalg.solve(H + lam * np.diag(d), -g)
@@ -57,6 +43,7 @@ def test_damped_step_of_the_blocked_ldlt(cams, calib, monkeypatch):
         steps = [h.lm_step(lam) for lam in lams]
         again = h.lm_step(lams[0])
         refs = [_dense_step(prob, h, lam) for lam in lams]
+        blocks = h.normal_equations()
     monkeypatch.setenv('MVUS_RCS_TRSM', 'launch')
     with BAHandle(prob) as h:
         h.residual_jacobian(x0, _lib.JAC_ANALYTIC)
@@ -68,6 +55,7 @@ def test_damped_step_of_the_blocked_ldlt(cams, calib, monkeypatch):
     with BAHandle(prob) as h:
         h.residual_jacobian(x0, _lib.JAC_ANALYTIC)
         gj = [h.lm_step(lam) for lam in lams]
+        gj_blocks = h.normal_equations()
     assert np.array_equal(steps[0], again), 'the solve is not reproducible run to run'
     for lam, p, q, r in zip(lams, steps, gj, refs):
         scale = np.abs(r).max()
@@ -75,6 +63,10 @@ def test_damped_step_of_the_blocked_ldlt(cams, calib, monkeypatch):
               % (nn, lam, np.abs(p - r).max() / scale, np.abs(q - r).max() / scale))
         np.testing.assert_allclose(p, r, rtol=0, atol=1e-7 * scale)
         np.testing.assert_allclose(p, q, rtol=0, atol=1e-7 * scale)
+        # ... and both held to the scaled backward error of LAPACK on the same blocks (lm_reference.eta_bound), each on the blocks
+        # its own handle exported
+        assert_backward_error(prob, *blocks, lam, p, 'nn = %d, L D L^T' % nn)
+        assert_backward_error(prob, *gj_blocks, lam, q, 'nn = %d, Gauss-Jordan' % nn, route_factor('rcs_gj'))
 
 
 def test_non_positive_pivot_raises_the_flag_and_lm_recovers():
@@ -130,6 +122,7 @@ def test_band_solver_without_back_correction(cams, calib, knots, monkeypatch):
     sc = synth.make_scene(cams, 120 * cams + 600, seed=300 + cams, rolling_shutter=True, num_knots=knots, opt_calib=calib)
     prob, x0 = mp.problem_from_scene(sc)
     lams = (1e-3, 0.7)
+    blocks = []
 
     def steps(env):
         for k in ('MVUS_PART_BACK', 'MVUS_DIRECT_RHS', 'MVUS_PART_LEN'):
@@ -140,13 +133,15 @@ def test_band_solver_without_back_correction(cams, calib, knots, monkeypatch):
             h.residual_jacobian(x0, _lib.JAC_ANALYTIC)
             out = [h.lm_step(lam) for lam in lams]
             ref = [_dense_step(prob, h, lam) for lam in lams] if not env else None
+            blocks.append(h.normal_equations())
         return out, ref
 
     new, refs = steps({})
     again, _ = steps({})
     old, _ = steps({'MVUS_PART_BACK': '1'})
     copy, _ = steps({'MVUS_DIRECT_RHS': '0'})
-    other_len, _ = steps({'MVUS_PART_LEN': '32' if prob.C * (3 + prob.P) <= 128 else '16'})
+    length = '32' if prob.C * (3 + prob.P) <= 128 else '16'
+    other_len, _ = steps({'MVUS_PART_LEN': length})
     for lam, p, a, o, c, l, r in zip(lams, new, again, old, copy, other_len, refs):
         scale = np.abs(r).max()
         assert np.array_equal(p, a), 'the solve is not reproducible run to run'
@@ -155,3 +150,6 @@ def test_band_solver_without_back_correction(cams, calib, knots, monkeypatch):
         np.testing.assert_allclose(p, r, rtol=0, atol=1e-7 * scale)
         for q in (o, c, l):
             np.testing.assert_allclose(p, q, rtol=0, atol=1e-8 * scale)
+        # ... and each held to the scaled backward error of LAPACK on the blocks its own handle exported (lm_reference.eta_bound)
+        for q, b, route in ((p, blocks[0], 'default'), (o, blocks[2], 'part_back'), (c, blocks[3], 'rhs_copy'), (l, blocks[4], 'part_len_%s' % length)):
+            assert_backward_error(prob, *b, lam, q, route, route_factor(route))

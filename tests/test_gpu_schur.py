@@ -4,6 +4,8 @@ import pytest
 
 from oracle import ba_oracle as orc
 from golden_util import CASES, load_case
+from lm_reference import assert_backward_error, backward_error
+from schur_reference import dense, internal_index
 from mvus_amd import _lib
 from mvus_amd import problem as mp
 
@@ -13,17 +15,6 @@ pytestmark = pytest.mark.gpu
 def _host(prob):
     from hostcheck_util import HostHandle
     return HostHandle(prob)
-
-
-def internal_index(prob):
-    """x index of every unknown in the solver's internal order: camera blocks (alpha,beta,rs,params), then 3*ctrl+xyz."""
-    C, P = prob.C, prob.P
-    cam = [[c, C + c, 2 * C + c] + list(range(3 * C + c * P, 3 * C + (c + 1) * P)) for c in range(C)]
-    spl = []
-    for s, n in enumerate(prob.n_coef):
-        for j in range(int(n)):
-            spl += [int(prob.spline_x_offsets[s]) + d * int(n) + j for d in range(3)]
-    return np.array(cam), np.array(spl)
 
 
 @pytest.mark.parametrize('name', CASES)
@@ -280,6 +271,7 @@ def test_lm_step_matches_sparse_direct_solve_on_a_long_chain():
     for lam, p in zip(lams, steps):
         p_ref = spla.spsolve(H + lam * sp.diags(d), -g)
         np.testing.assert_allclose(p, p_ref, rtol=0, atol=1e-7 * np.abs(p_ref).max())
+        assert_backward_error(prob, g, A, band, cross, lam, p, 'long chain')       # (blockwise: no n x n array at n = 7000)
 
 
 def test_damped_step_for_every_tail_length():
@@ -288,6 +280,7 @@ def test_damped_step_for_every_tail_length():
     from mvus_amd import synth
     from mvus_amd.ba import BAHandle
     worst = 0.0
+    worst_eta = (0.0,)
     seen = set()
     for nk in range(72, 150):
         sc = synth.make_scene(2, 700, seed=59, rolling_shutter=True, num_knots=nk)
@@ -296,27 +289,21 @@ def test_damped_step_for_every_tail_length():
         if N in seen:
             continue
         seen.add(N)
-        cam_idx, spl_idx = internal_index(prob)
         with BAHandle(prob) as h:
             h.residual_jacobian(x0, _lib.JAC_ANALYTIC)
             g, A, band, cross = h.normal_equations()
             p = h.lm_step(0.2)
-        n, C, B, W = prob.n_params, prob.C, 3 + prob.P, band.shape[1]
-        H = np.zeros((n, n))
-        for c in range(C):
-            H[np.ix_(cam_idx[c], cam_idx[c])] = A[c]
-        E = cross.reshape(C * B, 3 * N)
-        H[np.ix_(cam_idx.ravel(), spl_idx)] = E
-        H[np.ix_(spl_idx, cam_idx.ravel())] = E.T
-        for w in range(W):
-            for gi in range(N - w):
-                ri, cj = spl_idx[3 * gi:3 * gi + 3], spl_idx[3 * (gi + w):3 * (gi + w) + 3]
-                H[np.ix_(ri, cj)] = band[gi, w]
-                H[np.ix_(cj, ri)] = band[gi, w].T
+        H = dense(prob, g, A, band, cross)
         d = np.diag(H).copy()
         p_ref = np.linalg.solve(H + 0.2 * np.diag(np.where(d > 0, d, 1.0)), -g)
         worst = max(worst, float(np.abs(p - p_ref).max() / np.abs(p_ref).max()))
+        e, e_ref, bound = backward_error(prob, g, A, band, cross, 0.2, p, '%d control points' % N)
+        assert np.isfinite(p).all() and np.isfinite(e.eta), (N, e)          # (a NaN would win no comparison below)
+        if e.eta / bound >= worst_eta[0]:
+            worst_eta = (e.eta / bound, N, e, e_ref, bound)
     assert len(seen) > 60 and worst < 1e-8, (len(seen), worst)
+    # ... and, on the worst of the lengths, the scaled backward error against LAPACK's on the same blocks (lm_reference.eta_bound)
+    assert worst_eta[2].eta <= worst_eta[4], worst_eta
 
 
 @pytest.mark.parametrize('seed', range(8))
@@ -390,23 +377,11 @@ def test_schur_product_slab_plans(slabs, monkeypatch):
     prob, x0 = mp.problem_from_scene(sc)
     N = int(prob.n_coef.sum())
     assert (3 * N) % 16 != 0
-    cam_idx, spl_idx = internal_index(prob)
     with BAHandle(prob) as h:
         h.residual_jacobian(x0, _lib.JAC_ANALYTIC)
         g, A, band, cross = h.normal_equations()
         p = h.lm_step(0.05)
-    n, C, B, W = prob.n_params, prob.C, 3 + prob.P, band.shape[1]
-    H = np.zeros((n, n))
-    for c in range(C):
-        H[np.ix_(cam_idx[c], cam_idx[c])] = A[c]
-    E = cross.reshape(C * B, 3 * N)
-    H[np.ix_(cam_idx.ravel(), spl_idx)] = E
-    H[np.ix_(spl_idx, cam_idx.ravel())] = E.T
-    for w in range(W):
-        for gi in range(N - w):
-            ri, cj = spl_idx[3 * gi:3 * gi + 3], spl_idx[3 * (gi + w):3 * (gi + w) + 3]
-            H[np.ix_(ri, cj)] = band[gi, w]
-            H[np.ix_(cj, ri)] = band[gi, w].T
+    H = dense(prob, g, A, band, cross)
     d = np.diag(H).copy()
     p_ref = np.linalg.solve(H + 0.05 * np.diag(np.where(d > 0, d, 1.0)), -g)
     assert float(np.abs(p - p_ref).max() / np.abs(p_ref).max()) < 1e-8
