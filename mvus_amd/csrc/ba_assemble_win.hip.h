@@ -35,6 +35,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_kernels.hip.h"
+#include "ba_ne_views.h"
+#include "ba_wave.hip.h"
+
 namespace mvus {
 
 constexpr int kWinWaves = 4, kWinThreads = 64 * kWinWaves;
@@ -141,7 +145,6 @@ void k_assemble_windows(DevProblem dp, NEView ne, WinView wv, const CamState* __
   static_assert(NV * kWinStr <= REG, "staging fits the region");
   extern __shared__ double win_lds[];                       // per wavefront: [REG] staging / flush region, [32] masks; then the window's span records
   if (wv.mark != nullptr && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(wv.mark, wv.mark_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  using d4v = __attribute__((ext_vector_type(4))) double;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   double* S = win_lds + wave * WAVE;
@@ -250,13 +253,13 @@ void k_assemble_windows(DevProblem dp, NEView ne, WinView wv, const CamState* __
     const CamState& cam = cams[c];                          // wave-uniform: scalar loads
     int np0 = 0, np1 = 0;                                   // the next camera's range
     if (ci + 1 < ncam) cam_range(ci + 1, cnext, np0, np1);
-    d4v cacc[2][TI][TI];
+    d4 cacc[2][TI][TI];
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
-        for (int jj = 0; jj < TI; ++jj) cacc[h2][i][jj] = d4v{0.0, 0.0, 0.0, 0.0};
+        for (int jj = 0; jj < TI; ++jj) cacc[h2][i][jj] = d4{0.0, 0.0, 0.0, 0.0};
     double E[B];                                            // this lane's row (pl, d) of the camera's block of Et: across the camera's batches
 #pragma unroll
     for (int k = 0; k < B; ++k) E[k] = 0.0;

@@ -28,9 +28,11 @@
 #pragma once
 #include <climits>
 
+#include "ba_band_generic.hip.h"
 #include "ba_cov_math.h"
 #include "ba_detcov.hip.h"
-#include "ba_schur_hip.hip.h"
+#include "ba_ne_views.h"
+#include "ba_wave.hip.h"
 
 namespace mvus {
 
@@ -188,9 +190,9 @@ __global__ __launch_bounds__(256) void k_cov_tz(int N, int CB, const double* __r
   const int nchunk = (CB + 15) / 16, rounds = (nchunk + 3) / 4;
   for (int it = 0; it < rounds; ++it) {                     // (every wavefront makes every round: a chunk past the end reads zeros)
     const int j0 = (it * 4 + wave) * 16;
-    bcr_d4 acc[3];
+    d4 acc[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) acc[i] = bcr_d4{0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < 3; ++i) acc[i] = d4{0.0, 0.0, 0.0, 0.0};
     const bool jok = j0 + lr < CB;
     for (int k0 = 0; k0 < CB; k0 += 4) {
       const int k = k0 + lk;

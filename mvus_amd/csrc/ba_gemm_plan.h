@@ -1,4 +1,4 @@
-// Tiles and K-slabs of the Schur product (k_schur_gemm in ba_schur_hip.hip.h): which workgroup computes which 48x48 tile, where the
+// Tiles and K-slabs of the Schur product (k_schur_gemm in ba_schur_product.hip.h): which workgroup computes which 48x48 tile, where the
 // nine 16x16 accumulators of a tile go, and how many K-slabs the product is cut into.  Plain C++ (no HIP), shared by the kernel, its
 // host side and a stand-alone host check (tests/hostcheck/gemm_plan_hostcheck.cpp).
 #pragma once

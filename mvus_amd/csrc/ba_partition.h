@@ -1,4 +1,4 @@
-// Partition of the control-point chain for the band solver of ba_schur_hip.hip.h: plain host C++ (no HIP), so that the
+// Partition of the control-point chain for the band solver of ba_band_part.hip.h and ba_sep.hip.h: plain host C++ (no HIP), so that the
 // test-only host build can check its invariants.
 #pragma once
 #include <algorithm>

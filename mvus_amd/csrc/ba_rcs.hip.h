@@ -1,5 +1,6 @@
 // Reduced camera system S p_c = -rhs (dense, SPD, nn = C * (3 + P) <= 1152 unknowns): blocked L D L^T with the matrix held in the
-// register layout of the fp64 matrix cores.  Included by ba_schur_hip.hip.h (needs NEView, bcr_d4, ldl_inv16, dpp_shift).
+// register layout of the fp64 matrix cores.  NEView and the failure codes come from ba_ne_views.h, d4, lds_wave_sync
+// and ldl_inv16 from ba_wave.hip.h, dpp_shift from ba_kernels.hip.h.
 //
 // No counterpart in the reference (Scene.BA hands the whole problem to scipy, reconstruction/common.py:670); this replaces the
 // block Gauss-Jordan of rounds 1-4 (k_gj_step: one launch per 32 columns, 10.1 us each, of which the 32x32 pivot inverse in ONE
@@ -24,6 +25,11 @@
 // (block rows below: one wavefront per row, operands staged in LDS)  ->  k_rcs_syrk (trailing blocks, one wavefront each)  ->  next
 // super-panel ...  ->  k_rcs_backsub (one workgroup, descending).  nn = 288: 6 launches instead of 1 + 9.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include "ba_kernels.hip.h"
+#include "ba_ne_views.h"
+#include "ba_wave.hip.h"
 
 namespace mvus {
 
@@ -40,18 +46,18 @@ struct RcsView {
 
 __host__ __device__ __forceinline__ long long rcs_blk(int i, int j) { return ((long long)i * (i + 1) / 2 + j) * 256; }
 __host__ __device__ inline size_t rcs_doubles(int nn) { const int nbk = (nn + 15) / 16; return (size_t)rcs_blk(nbk + 1, 0); }
-__device__ __forceinline__ bcr_d4 rcs_load(const double* __restrict__ p) { return *reinterpret_cast<const bcr_d4*>(p); }
-__device__ __forceinline__ void rcs_store(double* __restrict__ p, bcr_d4 v) { *reinterpret_cast<bcr_d4*>(p) = v; }
+__device__ __forceinline__ d4 rcs_load(const double* __restrict__ p) { return *reinterpret_cast<const d4*>(p); }
+__device__ __forceinline__ void rcs_store(double* __restrict__ p, d4 v) { *reinterpret_cast<d4*>(p) = v; }
 // acc + P^T Q from img(P), img(Q)
-__device__ __forceinline__ bcr_d4 rcs_mma(bcr_d4 p, bcr_d4 q, bcr_d4 acc) {
+__device__ __forceinline__ d4 rcs_mma(d4 p, d4 q, d4 acc) {
 #pragma unroll
   for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(p[s], q[s], acc, 0, 0, 0);
   return acc;
 }
 // y = M w from img(M) and w[lr] (the value of this lane's column): the sums over the 16 lanes of a row by DPP row shifts;
 // lane lr == 15 of row lk ends with y[lk + 4r] in out[r]
-__device__ __forceinline__ bcr_d4 rcs_matvec(bcr_d4 img, double w) {
-  bcr_d4 out;
+__device__ __forceinline__ d4 rcs_matvec(d4 img, double w) {
+  d4 out;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     double v = img[r] * w;
@@ -64,7 +70,7 @@ __device__ __forceinline__ bcr_d4 rcs_matvec(bcr_d4 img, double w) {
   return out;
 }
 
-// L D L^T of a 16x16 block with the inverse factor, as ldl_inv16 (ba_schur_hip.hip.h: row i of the block and of the identity in lane i
+// L D L^T of a 16x16 block with the inverse factor, as ldl_inv16 (ba_wave.hip.h: row i of the block and of the identity in lane i
 // of every 16-lane row, multipliers by DPP row broadcast; same operations on every entry in the same order), with the instruction
 // order fixed BY HAND.  The unit of work is one (column K, target column J) pair: broadcast of the multiplier, the update of a[J] and
 // of x[J]; a scheduling barrier closes each.  Column K first updates column K + 1; the six dependent steps that turn the next pivot
@@ -210,17 +216,17 @@ struct RcsWide { rcs_u4 a, b; };
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rcs_rsrc(double* p, size_t doubles) {
   return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)(doubles * sizeof(double)), 0x00020000);
 }
-__device__ __forceinline__ void rcs_store_sc1(__amdgpu_buffer_rsrc_t r, long long dbl_off, bcr_d4 v) {
+__device__ __forceinline__ void rcs_store_sc1(__amdgpu_buffer_rsrc_t r, long long dbl_off, d4 v) {
   RcsWide w;
   __builtin_memcpy(&w, &v, sizeof(w));
   __builtin_amdgcn_raw_buffer_store_b128(w.a, r, (int)(dbl_off * 8), 0, 16);
   __builtin_amdgcn_raw_buffer_store_b128(w.b, r, (int)(dbl_off * 8 + 16), 0, 16);
 }
-__device__ __forceinline__ bcr_d4 rcs_load_sc1(__amdgpu_buffer_rsrc_t r, long long dbl_off) {
+__device__ __forceinline__ d4 rcs_load_sc1(__amdgpu_buffer_rsrc_t r, long long dbl_off) {
   RcsWide w;
   w.a = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(dbl_off * 8), 0, 16);
   w.b = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(dbl_off * 8 + 16), 0, 16);
-  bcr_d4 v;
+  d4 v;
   __builtin_memcpy(&v, &w, sizeof(v));
   return v;
 }
@@ -251,12 +257,12 @@ template <int J> struct RcsXtTimes {
 __device__ __forceinline__ double rcs_xt_times(const double* __restrict__ col, double w) { return RcsXtTimes<0>::run(col, w, 0.0); }
 // part = T_ik x_i for the block k of a row's register-resident blocks (k is wavefront-uniform but not a compile-time constant: the
 // nine-way selection is a scalar branch)
-__device__ __forceinline__ void rcs_part_product(const bcr_d4 (&sl)[kRcsSP], int k, const double* __restrict__ xi, double* __restrict__ out, int lr, int lk) {
+__device__ __forceinline__ void rcs_part_product(const d4 (&sl)[kRcsSP], int k, const double* __restrict__ xi, double* __restrict__ out, int lr, int lk) {
   const double xv = xi[lr];
 #pragma unroll
   for (int kk = 0; kk < kRcsSP; ++kk) {
     if (kk != k) continue;
-    const bcr_d4 y = rcs_matvec(sl[kk], xv);
+    const d4 y = rcs_matvec(sl[kk], xv);
     if (lr == 15) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) out[lk + 4 * r] = y[r];
@@ -287,11 +293,11 @@ __device__ __forceinline__ void rcs_pivot_role(int nc, int* __restrict__ fail, d
     // four 32-byte stores per lane of the first row instead of sixteen scattered 8-byte ones
     if (lane < 16) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) rcs_store(Xb + k * 256 + lane * 16 + 4 * q, bcr_d4{x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]});
+      for (int q = 0; q < 4; ++q) rcs_store(Xb + k * 256 + lane * 16 + 4 * q, d4{x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]});
     }
     if (lane == 0) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) rcs_store(rdb + k * 16 + 4 * q, bcr_d4{rd[4 * q], rd[4 * q + 1], rd[4 * q + 2], rd[4 * q + 3]});
+      for (int q = 0; q < 4; ++q) rcs_store(rdb + k * 16 + 4 * q, d4{rd[4 * q], rd[4 * q + 1], rd[4 * q + 2], rd[4 * q + 3]});
     }
     lds_barrier();                                                 // b1: X_k, 1/d_k
     lds_barrier();                                                 // b2: panel k and block (k + 1, k + 1)
@@ -314,8 +320,8 @@ __device__ __forceinline__ void rcs_trsm_role(RcsView rv, int c0, int nc, unsign
   const size_t tot = rcs_doubles(rv.nn);
   const __amdgpu_buffer_rsrc_t rS = rcs_rsrc(rv.Simg, tot), rT = rcs_rsrc(rv.Tsc, tot);
   constexpr int kSlots = (kRcsSP + kRcsTrsmWaves - 1) / kRcsTrsmWaves;
-  bcr_d4 s[kSlots];
-  const bcr_d4 zero{0.0, 0.0, 0.0, 0.0};
+  d4 s[kSlots];
+  const d4 zero{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int u = 0; u < kSlots; ++u) {
     const int jl = wave + kRcsTrsmWaves * u;
@@ -336,7 +342,7 @@ __device__ __forceinline__ void rcs_trsm_role(RcsView rv, int c0, int nc, unsign
     }
     lds_barrier();
     const bool dead = *abort_s != 0;
-    bcr_d4 tj[kSlots];
+    d4 tj[kSlots];
     bool up[kSlots];
 #pragma unroll
     for (int u = 0; u < kSlots; ++u) {
@@ -345,17 +351,17 @@ __device__ __forceinline__ void rcs_trsm_role(RcsView rv, int c0, int nc, unsign
       tj[u] = up[u] ? rcs_load_sc1(rS, rcs_blk(c0 + jl, c0 + k) + lane * 4) : zero;
     }
     if (wave == k % kRcsTrsmWaves && !dead) {
-      const bcr_d4 xi = rcs_load_sc1(rS, rcs_blk(c0 + k, c0 + k) + lane * 4);
-      bcr_d4 nrd;
+      const d4 xi = rcs_load_sc1(rS, rcs_blk(c0 + k, c0 + k) + lane * 4);
+      d4 nrd;
 #pragma unroll
       for (int r = 0; r < 4; ++r) nrd[r] = -rcs_load1_sc1(rT, rcs_blk(c0 + k, c0 + k) + lk + 4 * r);
-      const bcr_d4 t = rcs_mma(xi, s[k / kRcsTrsmWaves], zero);
+      const d4 t = rcs_mma(xi, s[k / kRcsTrsmWaves], zero);
       s[k / kRcsTrsmWaves] = t;
       rcs_store(xch + (k & 1) * 256 + lane * 4, t * nrd);
     }
     lds_barrier();
     if (k + 1 >= nc || dead) continue;
-    const bcr_d4 sc = rcs_load(xch + (k & 1) * 256 + lane * 4);
+    const d4 sc = rcs_load(xch + (k & 1) * 256 + lane * 4);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -366,7 +372,7 @@ __device__ __forceinline__ void rcs_trsm_role(RcsView rv, int c0, int nc, unsign
   for (int u = 0; u < kSlots; ++u) {                                 // the row's T blocks and their scaled images, for k_rcs_syrk / the substitution
     const int jl = wave + kRcsTrsmWaves * u;
     if (jl >= nc) continue;
-    bcr_d4 sc;
+    d4 sc;
 #pragma unroll
     for (int r = 0; r < 4; ++r) sc[r] = -rcs_load1_sc1(rT, rcs_blk(c0 + jl, c0 + jl) + lk + 4 * r) * s[u][r];
     rcs_store(rv.Simg + rcs_blk(gi, c0 + jl) + lane * 4, s[u]);
@@ -390,7 +396,7 @@ __device__ __forceinline__ void rcs_publisher_role(RcsView rv, int c0, int nc, u
       if (lane == 0) __hip_atomic_store(flags, (unsigned)(c0 * 16 + k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // steps 0 .. k - 1
     }
     lds_barrier();                                                   // b2: panel k complete
-    bcr_d4 xi;
+    d4 xi;
 #pragma unroll
     for (int r = 0; r < 4; ++r) xi[r] = Xb[k * 256 + (lk + 4 * r) * 16 + lr];
     rcs_store_sc1(rS, rcs_blk(c0 + k, c0 + k) + lane * 4, xi);
@@ -429,7 +435,7 @@ __global__ __launch_bounds__(kRcsFactorThreads) void k_rcs_factor(RcsView rv, in
     // the factors of the diagonal blocks, for the kernels that follow
     if (!last || c0 > 0)
       for (int k = 0; k < nc; ++k) {
-        bcr_d4 xi;
+        d4 xi;
 #pragma unroll
         for (int r = 0; r < 4; ++r) xi[r] = Xb[k * 256 + (lk + 4 * r) * 16 + lr];
         rcs_store(rv.Simg + rcs_blk(c0 + k, c0 + k) + lane * 4, xi);
@@ -463,8 +469,8 @@ __global__ __launch_bounds__(kRcsFactorThreads) void k_rcs_factor(RcsView rv, in
   const int il = wave;                                               // local block row; il == nc: the right-hand side
   const bool has = il <= nc, isR = il == nc;
   const int gi = isR ? R : c0 + il;
-  bcr_d4 sl[kRcsSP];
-  const bcr_d4 zero{0.0, 0.0, 0.0, 0.0};
+  d4 sl[kRcsSP];
+  const d4 zero{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int jl = 0; jl < kRcsSP; ++jl) sl[jl] = (has && jl < nc && (isR || jl <= il)) ? rcs_load(rv.Simg + rcs_blk(gi, c0 + jl) + lane * 4) : zero;
   if (wave == 0) {
@@ -479,12 +485,12 @@ __global__ __launch_bounds__(kRcsFactorThreads) void k_rcs_factor(RcsView rv, in
       const bool act = has && il > k;                                // (the right-hand side: il = nc > k)
       const bool owner = act && il == k + 1 && !isR && k + 1 < nc;   // this row's diagonal block is the next pivot block
       if (owner) __builtin_amdgcn_s_setprio(2);                      // its two products are the chain: ahead of the other rows' on this SIMD
-      bcr_d4 sc = zero;
+      d4 sc = zero;
       if (act) {
-        bcr_d4 xi;                                                   // img(X_k^T)[lane][s] = X_k[lr][lk + 4s]; Xb holds X column-major
+        d4 xi;                                                   // img(X_k^T)[lane][s] = X_k[lr][lk + 4s]; Xb holds X column-major
 #pragma unroll
         for (int r = 0; r < 4; ++r) xi[r] = Xb[k * 256 + (lk + 4 * r) * 16 + lr];
-        const bcr_d4 t = rcs_mma(xi, sl[k], zero);
+        const d4 t = rcs_mma(xi, sl[k], zero);
         sl[k] = t;
 #pragma unroll
         for (int r = 0; r < 4; ++r) sc[r] = -rdb[k * 16 + lk + 4 * r] * t[r];
@@ -501,7 +507,7 @@ __global__ __launch_bounds__(kRcsFactorThreads) void k_rcs_factor(RcsView rv, in
       }
       lds_barrier();                                                 // b2: panel k, block (k + 1, k + 1)
       {                                                              // the row's remaining blocks: K-slices outer, blocks inner
-        bcr_d4 tj[kRcsSP];
+        d4 tj[kRcsSP];
         bool up[kRcsSP];
 #pragma unroll
         for (int jl = k + 1; jl < kRcsSP; ++jl) {
@@ -522,7 +528,7 @@ __global__ __launch_bounds__(kRcsFactorThreads) void k_rcs_factor(RcsView rv, in
 #pragma unroll
   for (int k = 0; k < kRcsSP; ++k) {
     if (k < nc && il > k) {
-      bcr_d4 sc;
+      d4 sc;
 #pragma unroll
       for (int r = 0; r < 4; ++r) sc[r] = -rdb[k * 16 + lk + 4 * r] * sl[k][r];
       rcs_store(rv.Simg + rcs_blk(gi, c0 + k) + lane * 4, sl[k]);
@@ -565,7 +571,7 @@ __device__ __forceinline__ void rcs_stage(const RcsView& rv, int c0, int nc, dou
   double* rds = st + nc * 256;
   double* ts = rds + nc * 16;
   const int nblk = nc + nc * (nc - 1) / 2;
-  bcr_d4 v[kPer];
+  d4 v[kPer];
   double rdv[kPer];
   int dst[kPer];
 #pragma unroll
@@ -609,8 +615,8 @@ __global__ __launch_bounds__(64 * kRcsTrsmWaves) void k_rcs_trsm(RcsView rv, int
   double* xch = rcs_lds + rcs_stage_doubles(nc);                     // 2 x 256 doubles
   const int gi = c1 + blockIdx.x;
   constexpr int kSlots = (kRcsSP + kRcsTrsmWaves - 1) / kRcsTrsmWaves;
-  bcr_d4 s[kSlots];
-  const bcr_d4 zero{0.0, 0.0, 0.0, 0.0};
+  d4 s[kSlots];
+  const d4 zero{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int u = 0; u < kSlots; ++u) {
     const int jl = wave + kRcsTrsmWaves * u;
@@ -621,17 +627,17 @@ __global__ __launch_bounds__(64 * kRcsTrsmWaves) void k_rcs_trsm(RcsView rv, int
   for (int k = 0; k < kRcsSP; ++k) {
     if (k >= nc) continue;
     if (wave == k % kRcsTrsmWaves) {
-      const bcr_d4 t = rcs_mma(rcs_load(rcs_lds + k * 256 + lane * 4), s[k / kRcsTrsmWaves], zero);
+      const d4 t = rcs_mma(rcs_load(rcs_lds + k * 256 + lane * 4), s[k / kRcsTrsmWaves], zero);
       s[k / kRcsTrsmWaves] = t;
-      bcr_d4 sc;
+      d4 sc;
 #pragma unroll
       for (int r = 0; r < 4; ++r) sc[r] = -rds[k * 16 + lk + 4 * r] * t[r];
       rcs_store(xch + (k & 1) * 256 + lane * 4, sc);
     }
     lds_barrier();
     if (k + 1 >= nc) continue;
-    const bcr_d4 sc = rcs_load(xch + (k & 1) * 256 + lane * 4);
-    bcr_d4 tj[kSlots];
+    const d4 sc = rcs_load(xch + (k & 1) * 256 + lane * 4);
+    d4 tj[kSlots];
     bool up[kSlots];
 #pragma unroll
     for (int u = 0; u < kSlots; ++u) {
@@ -649,7 +655,7 @@ __global__ __launch_bounds__(64 * kRcsTrsmWaves) void k_rcs_trsm(RcsView rv, int
   for (int u = 0; u < kSlots; ++u) {                                 // (stores after the chain: see rcs_pivot_role)
     const int jl = wave + kRcsTrsmWaves * u;
     if (jl >= nc) continue;
-    bcr_d4 sc;
+    d4 sc;
 #pragma unroll
     for (int r = 0; r < 4; ++r) sc[r] = -rds[jl * 16 + lk + 4 * r] * s[u][r];
     rcs_store(rv.Simg + rcs_blk(gi, c0 + jl) + lane * 4, s[u]);
@@ -672,8 +678,8 @@ __global__ __launch_bounds__(256) void k_rcs_syrk(RcsView rv, int c0) {
   } else { il = m; jl = t - ntri; }
   const int gi = c1 + il, gj = c1 + jl;                              // (c1 + m = nbk: the right-hand-side row)
   double* blk = rv.Simg + rcs_blk(gi, gj) + lane * 4;
-  bcr_d4 acc = rcs_load(blk);
-  bcr_d4 pj[kRcsSP], qi[kRcsSP];
+  d4 acc = rcs_load(blk);
+  d4 pj[kRcsSP], qi[kRcsSP];
 #pragma unroll
   for (int k = 0; k < kRcsSP; ++k) {
     if (k >= nc) continue;
@@ -711,7 +717,7 @@ __global__ __launch_bounds__(64 * kRcsBackWaves) void k_rcs_backsub(RcsView rv, 
     double* ts = rds + nc * 16;
     const int nblk = nc + nc * (nc - 1) / 2;
     constexpr int kPer = (kRcsSP + kRcsSP * (kRcsSP - 1) / 2 + kRcsBackWaves - 1) / kRcsBackWaves;
-    bcr_d4 sv[kPer];
+    d4 sv[kPer];
     double srd[kPer];
     int sdst[kPer];
 #pragma unroll
@@ -737,12 +743,12 @@ __global__ __launch_bounds__(64 * kRcsBackWaves) void k_rcs_backsub(RcsView rv, 
       tR = rv.Simg[rcs_blk(R, c0 + jl) + ((row & 3) * 16) * 4 + (row >> 2)];            // column 0 of T_R,jl
     }
     const int nitem = (nbk - c1) * nc;
-    bcr_d4 img[kBatch];
+    d4 img[kBatch];
     double xv[kBatch];
 #pragma unroll
     for (int q = 0; q < kBatch; ++q) {
       const int it = min(wave + kRcsBackWaves * q, max(nitem - 1, 0)), i = c1 + it / nc, jl = it % nc;
-      img[q] = nitem > 0 ? rcs_load(rv.Simg + rcs_blk(i, c0 + jl) + lane * 4) : bcr_d4{0.0, 0.0, 0.0, 0.0};
+      img[q] = nitem > 0 ? rcs_load(rv.Simg + rcs_blk(i, c0 + jl) + lane * 4) : d4{0.0, 0.0, 0.0, 0.0};
       xv[q] = nitem > 0 ? xs[i * 16 + lr] : 0.0;
     }
     // ---- commit the stage, then the products of the rows below (partial sums per wavefront, added in wavefront order below)
@@ -768,7 +774,7 @@ __global__ __launch_bounds__(64 * kRcsBackWaves) void k_rcs_backsub(RcsView rv, 
         const int it = it0 + kRcsBackWaves * q;
         if (it >= nitem) continue;
         const int jl = it % nc;
-        const bcr_d4 y = rcs_matvec(img[q], xv[q]);
+        const d4 y = rcs_matvec(img[q], xv[q]);
         if (lr == 15) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) up[wave * kRcsSP * 16 + jl * 16 + lk + 4 * r] += y[r];
@@ -785,7 +791,7 @@ __global__ __launch_bounds__(64 * kRcsBackWaves) void k_rcs_backsub(RcsView rv, 
     lds_barrier();
     for (int k = nc - 1; k >= 0; --k) {
       if (wave == 0) {
-        const bcr_d4 y = rcs_matvec(rcs_load(st + k * 256 + lane * 4), rds[k * 16 + lr] * u[k * 16 + lr]);
+        const d4 y = rcs_matvec(rcs_load(st + k * 256 + lane * 4), rds[k * 16 + lr] * u[k * 16 + lr]);
         if (lr == 15) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) xs[(c0 + k) * 16 + lk + 4 * r] = y[r];
@@ -793,7 +799,7 @@ __global__ __launch_bounds__(64 * kRcsBackWaves) void k_rcs_backsub(RcsView rv, 
       }
       lds_barrier();
       if (wave < k) {                                                // jl = wave
-        const bcr_d4 y = rcs_matvec(rcs_load(ts + rcs_tri(k, wave) * 256 + lane * 4), xs[(c0 + k) * 16 + lr]);
+        const d4 y = rcs_matvec(rcs_load(ts + rcs_tri(k, wave) * 256 + lane * 4), xs[(c0 + k) * 16 + lr]);
         if (lr == 15) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) u[wave * 16 + lk + 4 * r] -= y[r];

@@ -315,7 +315,7 @@ def test_group_columns_rejects_bad_input_and_matches_scipy_on_a_random_pattern()
 
 
 def test_two_level_separator_elimination_algebra():
-    """The algebra behind the time shards' two-level elimination of the separators (mvus_amd/csrc/ba_schur_hip.hip.h: k_sep2_build /
+    """The algebra behind the time shards' two-level elimination of the separators (mvus_amd/csrc/ba_sep.hip.h: k_sep2_build /
     k_sep2_reduce / k_sep2_finish), in numpy on a random SPD block-tridiagonal system: every "rank" solves its LOCAL separators with the
     two coupling blocks as extra right-hand-side columns, contributes T'_G, U'_G, R'_G, T'_K, R'_K to the (world - 1)-node cut system,
     the cut system is solved once, and X_L = Y - V X_G - W X_K.  Must equal the direct solve -- including ranks without local separators

@@ -1,5 +1,5 @@
 // Cycle cost of the 16x16 L D L^T + inverse factor that sits on the critical path of the block Gauss-Jordan (ldl_inv16 in
-// ba_schur_hip.hip.h), one lone wavefront, three formulations; results checked against each other and against the host.
+// ba_wave.hip.h), one lone wavefront, three formulations; results checked against each other and against the host.
 // hipcc --offload-arch=gfx950 -O3 -o ldl16_bench ldl16_bench.hip && ./ldl16_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>
