@@ -147,7 +147,7 @@ void mvus_default_opts(mvus_solve_opts* opts);
  * sizeof(mvus_result), sizeof(mvus_problem) as this library was compiled (any pointer may be NULL) and returns MVUS_ABI_VERSION.  A
  * binding asserts these against its own struct definitions at load time -- mvus_solve_opts has grown over the rounds (lm_lambda_min,
  * lm_trust_radius) and a stale stub would otherwise hand the library a short buffer.  The version is raised whenever a struct or an
- * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance, mvus_ba_set_position_priors, mvus_ba_detection_covariance) does not raise
+ * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance, mvus_ba_set_position_priors, mvus_ba_detection_covariance, mvus_ba_set_landmarks) does not raise
  * it -- a binding that needs one finds it missing at load time.  Stateless, no device is touched.  No reference counterpart (the reference has no FFI). */
 #define MVUS_ABI_VERSION 8
 int32_t mvus_abi_sizes(int32_t* solve_opts_size, int32_t* result_size, int32_t* problem_size);
@@ -330,6 +330,44 @@ int mvus_ba_set_position_priors(mvus_ba* h, int64_t K, const double* t, const do
 int64_t mvus_ba_num_position_priors(const mvus_ba* h, int64_t* active_out);
 int mvus_ba_position_prior_cost(mvus_ba* h, const double* x, double* cost_out, double* r_out);
 
+/* Surveyed landmarks (ba_landmark.hip.h; no reference counterpart): L constant world points X_l -- ground control points -- and K
+ * observations (camera c_k, landmark l_k, raw pixel (u_k, v_k), weights (wu_k, wv_k) = 1 / sigma in pixels, 0: that axis is unknown).
+ * Observation k adds the two rows  r_k = w_k (.) (pi_c(X_l) - obs_k), signed, predicted minus observed, where pi_c and obs are what a
+ * detection row does with the spline point replaced by X_l: rotate, translate, divide, apply K; under fixed calibration with
+ * undist_points the observed pixel is undistorted once at set time, under opt_calib inside the row with the unknown K and d.  The rows
+ * have the P camera columns of a detection row (P = 6: rvec, t; P = 15: fx, fy, cx, cy, rvec, t, k1, k2, p1, p2, k3) and no others: no
+ * alpha / beta / rs, no control points, no visibility test (a landmark has no time), no cheirality test.  Three landmarks that are not
+ * collinear, seen by the cameras, fix the seven freedoms of the similarity gauge, the scale included.
+ *   X[3L] = x(L) y(L) z(L); cam[K], point[K]; uv[2K] = u(K) v(K); w[2K] in the same layout, in any order (the library sorts by
+ *   (camera, landmark, input order)); K = 0 or a NULL array clears.
+ * State of the handle, as the loss, the frozen mask and the position priors are: in force for every later mvus_ba_solve
+ * (MVUS_SOLVER_LM_SCHUR, every Jacobian mode) / mvus_ba_normal_equations / mvus_ba_lm_step / mvus_ba_covariance /
+ * mvus_ba_detection_covariance until set again, kept over mvus_ba_remove_outliers.  There
+ *   cost and initial_cost of mvus_result += 0.5 sum r^2;  camera block c gains sum J^T J on its P x P part and the camera gradient
+ *   sum J^T r on its P entries (J = d r / d camera parameters, weighted), in front of the freeze pass: held parameters stay held.  The
+ *   sync slots of the block, the cross block, the band, the spline gradient and other cameras' blocks are untouched.  The covariance's
+ *   dof counts one row per (observation, axis) with w > 0.
+ * The rows are plain L2: a robust loss in force reweights detection and motion rows only.  Everything about error_BA itself stays raw
+ * (2M + T rows), as do mvus_ba_robust_cost and mvus_ba_position_prior_cost.  Setting or clearing drops what an earlier LM solve carried
+ * over, as mvus_ba_set_loss does, and leaves the damping history alone; a handle without a weighted observation runs exactly the
+ * kernels it ran before this entry point existed.  The sums are formed by one writer per entry in sorted order: the same bits on every
+ * run, and for every order of the observations as long as no (camera, landmark) pair occurs twice.
+ * MVUS_E_INVALID, before the device is touched: L or K < 0, K > 2^24, a camera index outside [0, C), a landmark index outside [0, L), a
+ * non-finite X, uv or w, a negative weight.  MVUS_E_UNSUPPORTED: landmarks on a sharded handle ("sharded" in the message, here or --
+ * when the route is installed afterwards -- from the calls above); mvus_ba_solve with MVUS_SOLVER_TRF_LSMR while a weighted observation
+ * is set ("TRF_LSMR" in the message); mvus_ba_register_cameras / mvus_ba_register_linearize while observations are set ("landmark" in the
+ * message: their per-camera problems would drop rows that involve exactly that camera).
+ * Not offered: landmarks as unknowns, full 2 x 2 weights, landmarks inside the register problems, MVUS_SOLVER_TRF_LSMR, sharded handles.
+ * mvus_ba_num_landmark_observations: K as set; *rows_out (may be NULL) the rows with w > 0.
+ * mvus_ba_landmark_cost: 0.5 sum r^2 at x and, when r_out is not NULL, r[2K] = ru(K) rv(K) in the CALLER's order.
+ * mvus_ba_landmark_rows: r as above and J_out[K][2][P] = d r / d (camera parameters of c_k), weighted, in the caller's order (either may
+ * be NULL).  Both are inspection hooks on one rank: x is evaluated in a buffer of its own, the held Jacobian, its point, f and the blocks
+ * of the last mvus_ba_normal_equations stay as they are. */
+int mvus_ba_set_landmarks(mvus_ba* h, int64_t L, const double* X, int64_t K, const int32_t* cam, const int32_t* point, const double* uv, const double* w);
+int64_t mvus_ba_num_landmark_observations(const mvus_ba* h, int64_t* rows_out);
+int mvus_ba_landmark_cost(mvus_ba* h, const double* x, double* cost_out, double* r_out);
+int mvus_ba_landmark_rows(mvus_ba* h, const double* x, double* r_out, double* J_out);
+
 /* Covariance of the estimate at x (ba_cov.hip.h; no reference counterpart: scipy's least_squares returns none either).  With the loss and the
  * frozen mask in force, H is the matrix mvus_ba_normal_equations exports at x -- J^T J, or scipy's J^T diag(s^2) J under a robust loss (the
  * usual Gauss-Newton approximation then), the motion rows included as the prior they are.  An unknown is ESTIMATED when it is not frozen and
@@ -474,7 +512,8 @@ int mvus_ba_set_time_shard(mvus_ba* h, int32_t rank, int32_t world, const int32_
  *   the robust partial sums, motion rows and the final sum), 1 residual+Jacobian with the outputs ROTATING over >= 3 buffer sets (>= 1 GiB in rotation, so no
  *   launch writes into lines its predecessor left in the 256 MiB Infinity Cache), 2 J v, 3 J^T u, 4 normal-equation
  *   assembly from the materialised Jacobian, 5 residual+Jacobian re-launched into one buffer set (cache-resident variant,
- *   for comparison), 6 the fused Jacobian + normal-equation assembly of the LM path (no Jacobian in memory) */
+ *   for comparison), 6 the fused Jacobian + normal-equation assembly of the LM path (no Jacobian in memory), 7 the landmarks' cost kernel,
+ *   8 the landmarks' normal-equation kernel (7, 8: MVUS_E_INVALID without a weighted landmark observation) */
 int mvus_ba_time_kernel(mvus_ba* h, int32_t which, int32_t launches, double* avg_ms);
 
 /* Upload x to the handle without evaluating anything (used with mvus_ba_time_kernel). */

@@ -91,6 +91,10 @@ API = [
     ('mvus_ba_set_position_priors', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
     ('mvus_ba_num_position_priors', ctypes.c_int64, [ctypes.c_void_p, c_int64_p]),
     ('mvus_ba_position_prior_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ('mvus_ba_set_landmarks', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int64, c_int32_p, c_int32_p, c_double_p, c_double_p]),
+    ('mvus_ba_num_landmark_observations', ctypes.c_int64, [ctypes.c_void_p, c_int64_p]),
+    ('mvus_ba_landmark_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ('mvus_ba_landmark_rows', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
     ('mvus_ba_robust_cost', ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]),
     ('mvus_ba_covariance', ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_double_p, c_double_p, c_uint8_p, c_double_p, c_int64_p]),
     ('mvus_ba_covariance_stage_ms', ctypes.c_int32, [ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32]),

@@ -46,6 +46,32 @@ def position_prior_arrays(t, P, sigma):
     return t, P, w
 
 
+def landmark_arrays(X, cam, point, uv, sigma):
+    """(X (3, L), cam (K,), point (K,), uv (2, K), sigma scalar | (2,) | (2, K)) -> contiguous (X, cam int32, point int32, uv, w) with
+    w = 1 / sigma (0 for an infinite sigma).  Shapes, NaN and non-positive sigma raise ValueError here; the library checks the numbers
+    and the index ranges again."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != 3:
+        raise ValueError('landmarks: X has shape %s, expected (3, L)' % (X.shape,))
+    cam = np.ascontiguousarray(np.asarray(cam).ravel(), dtype=np.int32)
+    point = np.ascontiguousarray(np.asarray(point).ravel(), dtype=np.int32)
+    K = cam.size
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    if point.size != K or uv.shape != (2, K):
+        raise ValueError('landmarks: cam (%d,), point (%d,) and uv %s do not describe the same K observations' % (K, point.size, uv.shape))
+    s = np.asarray(sigma, dtype=np.float64)
+    if s.ndim == 1 and s.shape == (2,):
+        s = s[:, None]
+    elif s.ndim not in (0, 2) or (s.ndim == 2 and s.shape != (2, K)):
+        raise ValueError('landmarks: sigma has shape %s, expected a scalar, (2,) or (2, %d)' % (s.shape, K))
+    s = np.broadcast_to(s, (2, K))
+    if np.any(np.isnan(s)) or np.any(s <= 0):
+        raise ValueError('landmarks: sigma must be positive (np.inf leaves an axis out)')
+    with np.errstate(divide='ignore'):
+        w = np.ascontiguousarray(np.where(np.isinf(s), 0.0, 1.0 / s))
+    return X, cam, point, uv, w
+
+
 class UnsupportedBySolver(RuntimeError):
     """MVUS_E_UNSUPPORTED: the problem is outside what the chosen solver handles (see include/mvus_ba.h); the other solver has no such limit."""
 
@@ -324,6 +350,46 @@ class BAHandle:
         self._check(self.lib.mvus_ba_position_prior_cost(self.h, _lib.dptr(x), ctypes.byref(cost), _lib.dptr(r) if rows else None),
                     'mvus_ba_position_prior_cost')
         return (cost.value, r) if rows else cost.value
+
+    def set_landmarks(self, X, cam, point, uv, sigma):
+        """Surveyed static points as observations (mvus_ba_set_landmarks): ``X`` (3, L) world points, observation k = camera ``cam[k]``
+        (index on this handle) sees landmark ``point[k]`` at the raw pixel ``uv[:, k]``; ``sigma`` its 1-sigma in pixels as a scalar, per
+        axis (2,) or per axis and observation (2, K); ``np.inf`` leaves that axis out (weight 0).  Each observation adds the rows
+        (pi_c(X_l) - obs) / sigma to every later LM solve / normal_equations / lm_step / covariance on the handle, kept over
+        remove_outliers.  ``X = None`` (or K = 0) clears them."""
+        if X is None or cam is None or np.size(cam) == 0:
+            self._check(self.lib.mvus_ba_set_landmarks(self.h, 0, None, 0, None, None, None, None), 'mvus_ba_set_landmarks')
+            return
+        X, cam, point, uv, w = landmark_arrays(X, cam, point, uv, sigma)
+        self._check(self.lib.mvus_ba_set_landmarks(self.h, X.shape[1], _lib.dptr(X), cam.size, cam.ctypes.data_as(_lib.c_int32_p),
+                                                   point.ctypes.data_as(_lib.c_int32_p), _lib.dptr(uv), _lib.dptr(w)), 'mvus_ba_set_landmarks')
+
+    @property
+    def num_landmark_observations(self):
+        return int(self.lib.mvus_ba_num_landmark_observations(self.h, None))
+
+    @property
+    def num_landmark_rows(self):
+        a = ctypes.c_int64(0)
+        self.lib.mvus_ba_num_landmark_observations(self.h, ctypes.byref(a))
+        return int(a.value)
+
+    def landmark_cost(self, x, rows=False):
+        """0.5 sum r^2 of the landmark rows at x; with ``rows`` also r (2, K) in the order the observations were given."""
+        x = self._x(x, self.n)
+        cost = ctypes.c_double(0.0)
+        r = np.zeros((2, self.num_landmark_observations)) if rows else None
+        self._check(self.lib.mvus_ba_landmark_cost(self.h, _lib.dptr(x), ctypes.byref(cost), _lib.dptr(r) if rows else None), 'mvus_ba_landmark_cost')
+        return (cost.value, r) if rows else cost.value
+
+    def landmark_rows(self, x):
+        """(r (2, K), J (K, 2, P)): the weighted landmark rows at x and their derivatives w.r.t. the P parameters of each row's camera."""
+        x = self._x(x, self.n)
+        K = self.num_landmark_observations
+        r = np.zeros((2, K))
+        J = np.zeros((K, 2, self.prob.P))
+        self._check(self.lib.mvus_ba_landmark_rows(self.h, _lib.dptr(x), _lib.dptr(r), _lib.dptr(J)), 'mvus_ba_landmark_rows')
+        return r, J
 
     def robust_cost(self, x, weights=False):
         """0.5 f_scale^2 sum rho((f_i / f_scale)^2) at x under the loss in force; with ``weights`` also rho' of every row of f

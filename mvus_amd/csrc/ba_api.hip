@@ -55,6 +55,13 @@ static bool priors_on_shards(HipBackend& be, const char* who) {
   return true;
 }
 
+// and for landmarks
+static bool landmarks_on_shards(HipBackend& be, const char* who) {
+  if (be.lm.K <= 0 || !(be.allreduce || be.tshard.on)) return false;
+  be.err = std::string(who) + ": landmarks (mvus_ba_set_landmarks) are not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard)";
+  return true;
+}
+
 // the two timing entry points: `warmup` runs of fn, then the stream time of `reps` runs between two events, in ms per run
 template <class F>
 static double time_on_stream(hipStream_t st, int warmup, int reps, F&& fn) {
@@ -76,7 +83,8 @@ static double time_on_stream(hipStream_t st, int warmup, int reps, F&& fn) {
 // A new entry point picks its row here: kTransparent if it touches nothing the handle holds; kKeepsBlocks if the held Jacobian and the blocks
 // in the Schur workspace are written by HipSchur::assemble_held or not at all; else kKeepsNothing.            {carry, blocks}
 constexpr CallKeeps kTransparent{true, KeepBlocks::all};             // register_cameras, register_linearize
-constexpr CallKeeps kKeepsBlocks{false, KeepBlocks::all};            // normal_equations, lm_step, deterministic_fallback, position_prior_cost, lsmr, set_position_priors
+constexpr CallKeeps kKeepsBlocks{false, KeepBlocks::all};            // normal_equations, lm_step, deterministic_fallback, position_prior_cost, lsmr, set_position_priors,
+                                                                     // set_landmarks, landmark_cost, landmark_rows
 constexpr CallKeeps kKeepsRawBlocks{false, KeepBlocks::unfrozen};    // set_frozen: blocks with a freeze pass on them belong to the old mask
 constexpr CallKeeps kKeepsNothing{false, KeepBlocks::none};          // every other entry point: solve, covariance, detection_covariance, set_loss, ...
 
@@ -412,7 +420,7 @@ int mvus_ba_jtu(mvus_ba* h, const double* u, double* z) {
 
 int mvus_ba_normal_equations(mvus_ba* h, double* g, double* JtJ_cam, double* band, double* cross, int32_t* W_out) {
   return guarded(h, kKeepsBlocks, [&] {
-    if (frozen_on_shards(h->be, "normal_equations") || priors_on_shards(h->be, "normal_equations")) return MVUS_E_UNSUPPORTED;
+    if (frozen_on_shards(h->be, "normal_equations") || priors_on_shards(h->be, "normal_equations") || landmarks_on_shards(h->be, "normal_equations")) return MVUS_E_UNSUPPORTED;
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(h->be));
     return schur_export(h->be, *h->schur, g, JtJ_cam, band, cross, W_out);
   });
@@ -516,6 +524,86 @@ int mvus_ba_position_prior_cost(mvus_ba* h, const double* x, double* cost_out, d
   });
 }
 
+int mvus_ba_set_landmarks(mvus_ba* h, int64_t L, const double* X, int64_t K, const int32_t* cam, const int32_t* point, const double* uv, const double* w) {
+  return guarded(h, kKeepsBlocks, [&] {
+    HipBackend& be = h->be;
+    if (L < 0 || K < 0) { be.err = "set_landmarks: L or K < 0"; return MVUS_E_INVALID; }
+    if (K > (1ll << 24)) { be.err = "set_landmarks: more than 2^24 observations"; return MVUS_E_INVALID; }      // (2 K P stays inside int in the kernels' indices)
+    if (X == nullptr || cam == nullptr || point == nullptr || uv == nullptr || w == nullptr) K = 0;
+    if (K > 0 && L > (1ll << 28)) { be.err = "set_landmarks: more than 2^28 landmarks"; return MVUS_E_INVALID; }
+    for (int64_t k = 0; k < K; ++k) {
+      if (cam[k] < 0 || cam[k] >= be.hp.C) { be.err = "set_landmarks: cam[" + std::to_string(k) + "] = " + std::to_string(cam[k]) + " is not a camera of this handle"; return MVUS_E_INVALID; }
+      if (point[k] < 0 || point[k] >= L) { be.err = "set_landmarks: point[" + std::to_string(k) + "] = " + std::to_string(point[k]) + " is not a landmark"; return MVUS_E_INVALID; }
+    }
+    for (int64_t k = 0; k < (K > 0 ? 3 * L : 0); ++k)
+      if (!std::isfinite(X[k])) { be.err = "set_landmarks: X[" + std::to_string(k) + "] is not finite"; return MVUS_E_INVALID; }
+    for (int64_t k = 0; k < 2 * K; ++k) {
+      if (!std::isfinite(uv[k])) { be.err = "set_landmarks: uv[" + std::to_string(k) + "] is not finite"; return MVUS_E_INVALID; }
+      if (!std::isfinite(w[k]) || w[k] < 0.0) { be.err = "set_landmarks: w[" + std::to_string(k) + "] is not a finite weight >= 0"; return MVUS_E_INVALID; }
+    }
+    if (K > 0 && (be.allreduce || be.tshard.on)) {
+      be.err = "set_landmarks: landmarks are not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard)";
+      return MVUS_E_UNSUPPORTED;
+    }
+    // what an LM solve left for its point belongs to the OLD set of rows: not kept, as with mvus_ba_set_position_priors (blocks of the held
+    // Jacobian stay usable: the landmarks' pass goes on top, HipSchur::assemble_held); the damping history stays
+    be.set_landmarks(L, X, K, cam, point, uv, w);
+    return MVUS_OK;
+  });
+}
+
+int64_t mvus_ba_num_landmark_observations(const mvus_ba* h, int64_t* rows_out) {
+  if (!h) return -1;
+  if (rows_out) *rows_out = h->be.lm_rows;
+  return h->be.lm.K;
+}
+
+// the two inspection hooks: x goes to a buffer of its own and the cameras are decoded there -- x_cur, the held Jacobian, f_cur and the blocks
+// HipSchur holds stay as they are (the cached camera states are decoded again by whoever needs them next)
+static int landmark_inspect(mvus_ba* h, const char* who, const double* x, double* cost_out, double* r_out, double* J_out) {
+  return guarded(h, kKeepsBlocks, [&] {
+    HipBackend& be = h->be;
+    if (!x || (!cost_out && !r_out && !J_out)) { be.err = std::string(who) + ": NULL argument"; return MVUS_E_INVALID; }
+    if (landmarks_on_shards(be, who)) return MVUS_E_UNSUPPORTED;
+    const int64_t K = be.lm.K, P = be.hp.P;
+    if (cost_out) *cost_out = 0.0;
+    if (K <= 0) return MVUS_OK;
+    PoolGuard<HipBackend> pool(be);
+    double* xd = pool.get(be.hp.n);
+    be.upload(xd, x, be.hp.n);
+    double* r = pool.get(2 * K);
+    double* J = J_out ? pool.get(2 * K * P) : nullptr;
+    be.ensure_cams(xd);
+    const int lb = (int)std::min<int64_t>(2048, (K + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(k_landmark_cost, dim3(lb), dim3(kThreads), 0, be.stream, be.dp, be.lm, (const CamState*)be.cams, be.partials, r, J);
+    hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kThreads), 0, be.stream, lb, (const double*)be.partials, be.scal_out() + be.kLandmarkCostSlot);
+    MVUS_HIP(hipGetLastError());
+    const double twice = be.read_slot(be.kLandmarkCostSlot);
+    if (cost_out) *cost_out = 0.5 * twice;
+    if (r_out) {
+      std::vector<double> rs((size_t)2 * K);
+      be.download(rs.data(), r, 2 * K);
+      for (int64_t k = 0; k < K; ++k)
+        for (int d = 0; d < 2; ++d) r_out[d * K + be.lm_perm[(size_t)k]] = rs[(size_t)(d * K + k)];
+    }
+    if (J_out) {
+      std::vector<double> Js((size_t)(2 * K * P));
+      be.download(Js.data(), J, 2 * K * P);
+      for (int64_t k = 0; k < K; ++k) std::memcpy(J_out + be.lm_perm[(size_t)k] * 2 * P, Js.data() + k * 2 * P, sizeof(double) * 2 * P);
+    }
+    return MVUS_OK;
+  });
+}
+
+int mvus_ba_landmark_cost(mvus_ba* h, const double* x, double* cost_out, double* r_out) {
+  if (h && !cost_out) { h->be.err = "landmark_cost: NULL argument"; return MVUS_E_INVALID; }
+  return landmark_inspect(h, "landmark_cost", x, cost_out, r_out, nullptr);
+}
+
+int mvus_ba_landmark_rows(mvus_ba* h, const double* x, double* r_out, double* J_out) {
+  return landmark_inspect(h, "landmark_rows", x, nullptr, r_out, J_out);
+}
+
 int mvus_ba_robust_cost(mvus_ba* h, const double* x, double* cost_out, double* weights_out) {
   return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
@@ -599,7 +687,7 @@ int mvus_ba_lm_step(mvus_ba* h, double lambda, double* p_out) {
     HipBackend& be = h->be;
     if (!p_out || !(lambda >= 0)) { be.err = "lm_step: bad arguments"; return MVUS_E_INVALID; }
     if (!be.has_jacobian) { be.err = "no Jacobian held: call mvus_ba_residual_jacobian first"; return MVUS_E_INVALID; }
-    if (frozen_on_shards(be, "lm_step") || priors_on_shards(be, "lm_step")) return MVUS_E_UNSUPPORTED;
+    if (frozen_on_shards(be, "lm_step") || priors_on_shards(be, "lm_step") || landmarks_on_shards(be, "lm_step")) return MVUS_E_UNSUPPORTED;
     if (be.hp.C * (3 + be.hp.P) > 1152) throw HipError{"LM_SCHUR: reduced camera system larger than 1152 unknowns"};
     if (!h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
     HipSchur<HipBackend>& sc = *h->schur;
@@ -696,7 +784,11 @@ int mvus_ba_solve(mvus_ba* h, double* x, const mvus_solve_opts* opts, mvus_resul
                                                               : nullptr;
       if (what) { be.err = std::string("a robust loss (mvus_ba_set_loss) is not supported with ") + what + ": MVUS_SOLVER_LM_SCHUR with MVUS_JAC_ANALYTIC on one rank only"; return MVUS_E_UNSUPPORTED; }
     }
-    if (frozen_on_shards(be, "solve") || priors_on_shards(be, "solve")) return MVUS_E_UNSUPPORTED;
+    if (frozen_on_shards(be, "solve") || priors_on_shards(be, "solve") || landmarks_on_shards(be, "solve")) return MVUS_E_UNSUPPORTED;
+    if (be.lm_active > 0 && opts->solver != MVUS_SOLVER_LM_SCHUR) {         // never solved with the landmarks silently dropped
+      be.err = "landmarks (mvus_ba_set_landmarks) are not supported with MVUS_SOLVER_TRF_LSMR: MVUS_SOLVER_LM_SCHUR only";
+      return MVUS_E_UNSUPPORTED;
+    }
     if (be.prior_active > 0 && opts->solver != MVUS_SOLVER_LM_SCHUR) {      // never solved with the priors silently dropped
       be.err = "position priors (mvus_ba_set_position_priors) are not supported with MVUS_SOLVER_TRF_LSMR: MVUS_SOLVER_LM_SCHUR only";
       return MVUS_E_UNSUPPORTED;
@@ -764,6 +856,8 @@ static int register_call(mvus_ba* h, const char* who, const double* x, int32_t B
     if (reg_check_batch(who, be.hp.C, be.hp.P, B, cam, start, msg, sizeof msg)) { be.err = msg; return MVUS_E_INVALID; }
     if (!x) { be.err = std::string(who) + ": x is NULL"; return MVUS_E_INVALID; }
     if (be.allreduce || be.tshard.on) { be.err = std::string(who) + ": not supported on a sharded handle (set_allreduce / set_rccl / set_time_shard): one rank only"; return MVUS_E_UNSUPPORTED; }
+    // the per-camera problems hold the detection rows only: with landmarks set they would drop rows that involve exactly that camera
+    if (be.lm.K > 0) { be.err = std::string(who) + ": not supported while landmark observations are set (mvus_ba_set_landmarks): clear them first"; return MVUS_E_UNSUPPORTED; }
     if (!h->reg) h->reg.reset(new RegisterWork());
     return register_run(be, *h->reg, x, B, cam, start, o, linearize_only, out);
   });
@@ -940,7 +1034,8 @@ int mvus_ba_set_time_shard(mvus_ba* h, int32_t rank, int32_t world, const int32_
 int mvus_ba_time_kernel(mvus_ba* h, int32_t which, int32_t launches, double* avg_ms) {
   return guarded(h, kKeepsNothing, [&] {
     HipBackend& be = h->be;
-    if (launches < 1 || !avg_ms || which < 0 || which > 6) { be.err = "bad arguments"; return MVUS_E_INVALID; }
+    if (launches < 1 || !avg_ms || which < 0 || which > 8) { be.err = "bad arguments"; return MVUS_E_INVALID; }
+    if (which >= 7 && be.lm_active <= 0) { be.err = "time_kernel: which = 7 / 8 need landmark observations (mvus_ba_set_landmarks)"; return MVUS_E_INVALID; }
     be.ensure_J();
     PoolGuard<HipBackend> pool(be);
     double* vn = pool.get(be.hp.n); double* um = pool.get(be.hp.m); double* zn = pool.get(be.hp.n); double* ym = pool.get(be.hp.m);
@@ -949,7 +1044,7 @@ int mvus_ba_time_kernel(mvus_ba* h, int32_t which, int32_t launches, double* avg
     if (which >= 2 && which <= 4 && !be.has_jacobian) be.jacobian(be.x_cur, be.f_cur, MVUS_JAC_ANALYTIC);
     if (which == 6) be.residual(be.x_cur, be.f_cur);
     const dim3 g(std::max(be.dp.n_chunks, 1)), b(kThreads);
-    if ((which == 4 || which == 6) && !h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
+    if ((which == 4 || which == 6 || which == 8) && !h->schur) h->schur.reset(new HipSchur<HipBackend>(be));
     HipSchur<HipBackend>* schur = h->schur.get();
     // which == 1: the outputs (J, span, f) rotate over enough buffer sets that the bytes written between two uses of a
     // set exceed the 256 MiB Infinity Cache several times -- every launch writes to HBM, not into lines the previous
@@ -991,6 +1086,13 @@ int mvus_ba_time_kernel(mvus_ba* h, int32_t which, int32_t launches, double* avg
           break;
         case 6:
           schur->assemble_local(be.f_cur, be.x_cur);       // Jacobian evaluated inside the assembly (the LM path)
+          break;
+        case 7:
+          be.ensure_cams(be.x_cur);
+          hipLaunchKernelGGL(k_landmark_cost, dim3(be.landmark_blocks()), b, 0, be.stream, be.dp, be.lm, (const CamState*)be.cams, be.partials, (double*)nullptr, (double*)nullptr);
+          break;
+        case 8:
+          be.landmark_normal_equations(schur->ne, be.x_cur);      // (adds into the workspace over and over: the blocks there are no normal equations afterwards, and no call keeps them)
           break;
         default:
           schur->assemble_local(be.f_cur);

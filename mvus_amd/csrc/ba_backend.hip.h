@@ -19,6 +19,7 @@
 #include "ba_schur.h"
 #include "ba_switches.h"
 #include "ba_prior.hip.h"
+#include "ba_landmark.hip.h"
 
 namespace mvus {
 
@@ -59,13 +60,15 @@ struct HipBackend {
     kRowCountSlot = 2,                        // the global row count on its way over the ranks (reduce_row_count)
     kCostSlot = 3,                            // a one-off cost: mvus_ba_robust_cost, mvus_ba_covariance, mvus_ba_time_kernel
     kPriorCostSlot = 4,                       // mvus_ba_position_prior_cost
+    kLandmarkCostSlot = 5,                    // mvus_ba_landmark_cost
     kLmBase = 8,                              // the LM driver's block (LmSlot of ba_schur.h): lm_scalars()
     kFailSumSlot = kLmBase + kLmFailSum,      // ... whose tail is a time shard's failure sums: fetched with the trial's scalars
     kHostSumEnd = kFailSumSlot,               // residual_sq leaves a sum written below this slot to the host (fetch adds the partials)
     kMarkSlot = 24,                           // the start mark of fetch_poll_begin
     kScalCount = 32
   };
-  static_assert(kDotNSlot < kDotMSlot && kDotMSlot < kRowCountSlot && kRowCountSlot < kCostSlot && kCostSlot < kPriorCostSlot && kPriorCostSlot < kLmBase,
+  static_assert(kDotNSlot < kDotMSlot && kDotMSlot < kRowCountSlot && kRowCountSlot < kCostSlot && kCostSlot < kPriorCostSlot && kPriorCostSlot < kLandmarkCostSlot &&
+                    kLandmarkCostSlot < kLmBase,
                 "one user per slot in front of the LM block");
   static_assert(kLmFailSum == kLmStepPSq + 1 && kLmSlots == kLmFailSum + 2, "the failure sums directly follow the trial's scalars: one fetch covers both");
   static_assert(kCostSlot < kHostSumEnd && kLmBase + kLmTrialCost < kHostSumEnd && kHostSumEnd <= kMarkSlot, "the host-summed range holds every |f|^2 slot and not the mark");
@@ -582,14 +585,82 @@ struct HipBackend {
     hipLaunchKernelGGL(k_prior_ne, dim3((unsigned)((ne.N + kWaves - 1) / kWaves)), dim3(kThreads), 0, stream, dp, prior, x, ne);
     MVUS_HIP(hipGetLastError());
   }
+  // Surveyed landmarks (mvus_ba_set_landmarks, ba_landmark.hip.h), state of the handle like the loss, the mask and the priors, kept over
+  // remove_outliers (they hang on the cameras, which outlier removal leaves alone).  lm.K counts what the caller set, lm_active the
+  // observations with a weight on at least one axis: with lm_active = 0 no kernel, argument or branch on the device differs from a
+  // handle that never had any.
+  LandmarkView lm{};
+  DeviceOwner lm_own;
+  std::vector<int64_t> lm_perm;             // sorted position -> the caller's index
+  int lm_active = 0;
+  uint64_t lm_gen = 0, lm_sets = 0;         // lm_gen names the set in force (HipSchur::assemble_held: which landmarks held blocks carry)
+  int64_t lm_rows = 0;                      // (observation, axis) pairs with w > 0: the rows the covariance's degrees of freedom count
+  bool lm_lds_set = false;
+  int landmark_blocks() const { return lm_active > 0 ? (int)std::min<int64_t>(2048, ((int64_t)lm.K + kThreads - 1) / kThreads) : 0; }
+  void clear_landmarks() {
+    if (!lm_own.empty()) MVUS_HIP(hipStreamSynchronize(stream));
+    lm_own.reset(); lm_perm.clear();
+    lm = LandmarkView{}; lm_active = 0; lm_rows = 0;
+  }
+  template <class T>
+  T* lm_upload(const std::vector<T>& v) {
+    T* p = lm_own.device<T>(std::max<size_t>(v.size(), 1));
+    if (!v.empty()) MVUS_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+    return p;
+  }
+  // X[3L], cam[K], point[K], uv[2K], w[2K] in the caller's order (validated): sorted by (camera, landmark, input order), the rows per
+  // camera from the sorted list, the observed pixels of the fixed-calibration row by k_landmark_setup
+  void set_landmarks(int64_t L, const double* X, int64_t K, const int32_t* cam, const int32_t* point, const double* uv, const double* w) {
+    if (K <= 0) { clear_landmarks(); return; }
+    std::vector<int64_t> perm((size_t)K);
+    for (int64_t k = 0; k < K; ++k) perm[(size_t)k] = k;
+    std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return cam[a] != cam[b] ? cam[a] < cam[b] : point[a] < point[b]; });
+    std::vector<int32_t> cs((size_t)K), ps((size_t)K), lo((size_t)hp.C, 0), hi((size_t)hp.C, 0);
+    std::vector<double> uvs((size_t)2 * K), ws((size_t)2 * K);
+    const std::vector<double> Xs(X, X + 3 * L);
+    int active = 0;
+    int64_t rows = 0;
+    for (int64_t k = 0; k < K; ++k) {
+      const int64_t s = perm[(size_t)k];
+      cs[(size_t)k] = cam[s]; ps[(size_t)k] = point[s];
+      for (int d = 0; d < 2; ++d) { uvs[(size_t)(d * K + k)] = uv[d * K + s]; ws[(size_t)(d * K + k)] = w[d * K + s]; if (w[d * K + s] > 0.0) ++rows; }
+      if (w[s] > 0.0 || w[K + s] > 0.0) ++active;
+      if (hi[(size_t)cam[s]] == 0) lo[(size_t)cam[s]] = (int32_t)k;
+      hi[(size_t)cam[s]] = (int32_t)k + 1;
+    }
+    clear_landmarks();
+    LandmarkView lv{};      // built aside: a failure below leaves the handle without landmarks (the buffers go at the next clear_landmarks)
+    lv.K = (int)K; lv.L = (int)L;
+    lv.X = lm_upload(Xs); lv.cam = lm_upload(cs); lv.point = lm_upload(ps); lv.uv = lm_upload(uvs); lv.w = lm_upload(ws);
+    lv.uvo = lm_upload(uvs);
+    lv.row_lo = lm_upload(lo); lv.row_hi = lm_upload(hi);
+    if (!hp.calib && hp.undist) {
+      hipLaunchKernelGGL(k_landmark_setup, dim3((unsigned)((K + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, dp, lv);
+      MVUS_HIP(hipGetLastError());
+    }
+    if (!lm_lds_set) {      // (the attribute belongs to the function, not to the handle: the larger of the two sizes, whatever this handle's P)
+      MVUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_landmark_ne), hipFuncAttributeMaxDynamicSharedMemorySize, (int)landmark_lds_bytes(15)));
+      lm_lds_set = true;
+    }
+    MVUS_HIP(hipStreamSynchronize(stream));      // (pageable sources of asynchronous copies: alive until here)
+    lm = lv; lm_perm = perm; lm_active = active; lm_rows = rows; lm_gen = ++lm_sets;
+  }
+  // behind an assembly at x (HipSchur::assemble): the landmarks' blocks are added to the camera blocks and the camera gradient
+  void landmark_normal_equations(const NEView& ne, const double* x) {
+    if (x == nullptr || ne.C != hp.C || ne.B != 3 + hp.P) throw HipError{"landmarks: the assembly has no point, or is not this handle's camera block (internal error)"};
+    ensure_cams(x);
+    hipLaunchKernelGGL(k_landmark_ne, dim3((unsigned)hp.C), dim3(kThreads), landmark_lds_bytes(hp.P), stream, dp, lm, (const CamState*)cams, ne);
+    MVUS_HIP(hipGetLastError());
+  }
   // clr / clr_len: storage to zero beside the evaluation (HipSchur's normal-equation blocks); returns false if it was not done
-  // with_priors: the position priors' rows are part of the sum (every cost the solver and the covariance use; mvus_ba_robust_cost stays raw)
+  // with_priors: the position priors' and the landmarks' rows are part of the sum (every cost the solver and the covariance use;
+  // mvus_ba_robust_cost stays raw)
   bool residual_sq(const double* x, double* f, double* out, double* clr = nullptr, int64_t clr_len = 0, bool with_priors = true) {
     // (observation shards off the root rank: the replicated motion rows are rows of zeros there -- the general path)
     if (allreduce && hp.T > 0 && !(is_root || tshard.on)) { residual(x, f); dot_m_into(f, f, out); return false; }
     RoctxRange range("mvus residual");
     const int mb = hp.T > 0 ? (int)((hp.T + kThreads - 1) / kThreads) : 0;
-    const int pb = with_priors ? prior_blocks() : 0;
+    const int pb = with_priors ? prior_blocks() + landmark_blocks() : 0;      // (the landmarks' partials behind the priors')
     const size_t need = (size_t)dp.n_chunks + mb + pb + 1;
     const bool host_sum = scal_direct() && out >= scal_out() && out < scal_out() + kHostSumEnd && !sw.sq_device_sum;
     const int set = (out == lm_scalars() + kLmCostX0) ? 0 : 1;
@@ -620,7 +691,9 @@ struct HipBackend {
     }
     if (mb > 0 && robust()) hipLaunchKernelGGL((k_motion<false, true>), dim3(mb), dim3(kThreads), 0, stream, dp, x, f + 2 * hp.M, mJ, mctrl, 0, sq_part + dp.n_chunks, loss);
     else if (mb > 0) hipLaunchKernelGGL(k_motion<false>, dim3(mb), dim3(kThreads), 0, stream, dp, x, f + 2 * hp.M, mJ, mctrl, 0, sq_part + dp.n_chunks);
-    if (pb > 0) hipLaunchKernelGGL(k_prior_cost, dim3(pb), dim3(kThreads), 0, stream, dp, prior, x, sq_part + dp.n_chunks + mb, (double*)nullptr);
+    if (with_priors && prior_blocks() > 0) hipLaunchKernelGGL(k_prior_cost, dim3(prior_blocks()), dim3(kThreads), 0, stream, dp, prior, x, sq_part + dp.n_chunks + mb, (double*)nullptr);
+    if (with_priors && landmark_blocks() > 0)
+      hipLaunchKernelGGL(k_landmark_cost, dim3(landmark_blocks()), dim3(kThreads), 0, stream, dp, lm, (const CamState*)cams, sq_part + dp.n_chunks + mb + prior_blocks(), (double*)nullptr, (double*)nullptr);
     if (host_sum) { sq_pend[set].slot = out - scal_out(); sq_pend[set].n = dp.n_chunks + mb + pb; }      // added up by fetch()
     else if (dp.n_chunks + mb + pb > 0) hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(kThreads), 0, stream, dp.n_chunks + mb + pb, sq_part, out);
     else MVUS_HIP(hipMemsetAsync(out, 0, sizeof(double), stream));

@@ -405,7 +405,7 @@ struct CovChain {
     }
     int64_t n_est = (int64_t)map_h.size();
     for (int r = 0; r < ne.N3; ++r) if (dh[(size_t)(ne.CB + r)] != 0.0) { eh[(size_t)(ne.CB + r)] = 1; ++n_est; }
-    int64_t m_act = hp.T + be.prior_rows;      // (position priors: one row per active (prior, axis) with a weight)
+    int64_t m_act = hp.T + be.prior_rows + be.lm_rows;      // (position priors: one row per active (prior, axis) with a weight; landmarks: per (observation, axis))
     for (int64_t i = 0; i < hp.M; ++i) if (span_h[(size_t)i] >= 0) m_act += 2;
     res.dof = m_act - n_est;
     if (estimated) {

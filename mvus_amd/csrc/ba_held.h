@@ -24,8 +24,9 @@ namespace mvus {
 
 enum class KeepBlocks { none, unfrozen, all };      // unfrozen: only blocks without a freeze pass on them (mvus_ba_set_frozen: frozen ones belong to the old mask)
 struct CallKeeps { bool carry; KeepBlocks blocks; };
-// what was applied to the blocks a call left: the freeze pass, the fused (window-major) or the from-J assembly, the priors' generation (0: none)
-struct BlocksTag { bool frozen = false, fused = false; uint64_t prior_gen = 0; };
+// what was applied to the blocks a call left: the freeze pass, the fused (window-major) or the from-J assembly, the priors' generation (0: none),
+// the landmarks' generation (0: none)
+struct BlocksTag { bool frozen = false, fused = false; uint64_t prior_gen = 0, landmark_gen = 0; };
 struct LmDamping { double lambda = 0, nu = 0; };      // 0: where a fresh handle starts
 
 struct HandleMemory {
@@ -75,13 +76,15 @@ struct HandleMemory {
 
   // ---- the blocks of the held Jacobian, as the previous call left them in the Schur workspace ----
   // Under a mask or priors they are assembled ONCE: blocks the call before this one left (and every call since kept) are used again when
-  // they differ from the wanted ones by passes that go ON TOP only -- the priors' pass where they carry none (never other priors), the
-  // freeze pass where they are raw (never the other way).  Without a mask and without priors every call assembles, as always.
+  // they differ from the wanted ones by passes that go ON TOP only -- the priors' pass where they carry none (never other priors), the landmarks' pass
+  // where they carry none (never other landmarks; it writes the camera blocks, so on frozen blocks the caller runs the freeze pass again
+  // behind it: HipSchur::assemble_held), the freeze pass where they are raw (never the other way).  Without a mask and without priors every call assembles, as always.
   bool blocks_of_this_call() const { return held_seq != 0 && held_seq == seq; }
   const BlocksTag& held_blocks() const { return held; }
   bool blocks_reusable(const BlocksTag& want) const {
-    return (want.frozen || want.prior_gen != 0) && blocks_of_this_call() && held.fused == want.fused &&
-           (held.prior_gen == 0 || held.prior_gen == want.prior_gen) && (!held.frozen || want.frozen);
+    return (want.frozen || want.prior_gen != 0 || want.landmark_gen != 0) && blocks_of_this_call() && held.fused == want.fused &&
+           (held.prior_gen == 0 || held.prior_gen == want.prior_gen) && (held.landmark_gen == 0 || held.landmark_gen == want.landmark_gen) &&
+           (!held.frozen || want.frozen);
   }
   void stamp_blocks(const BlocksTag& tag) { held_seq = seq; held = tag; }
   void forget_blocks() { held_seq = 0; held = {}; }      // the workspace that held them is gone

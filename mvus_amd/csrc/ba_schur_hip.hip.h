@@ -19,7 +19,8 @@
 //
 // Assembly (HipSchur::assemble*): window-major, every entry stored once (ba_assemble_win.hip.h: k_assemble_windows, k_cam_block_sum) |
 // MVUS_ASM_ATOMIC, MVUS_NE_FROM_J: detection-major (ba_assemble.hip.h: k_assemble_spans, k_cam_block_reduce); then the motion rows
-// (k_det_motion | k_det_motion_wide | k_assemble_motion), k_freeze_ne, and on time shards k_halo_copy (ba_assemble.hip.h).
+// (k_det_motion | k_det_motion_wide | k_assemble_motion), the position priors' pass (ba_prior.hip.h: k_prior_ne) and the landmarks' pass
+// (ba_landmark.hip.h: k_landmark_ne) where a handle carries them, k_freeze_ne, and on time shards k_halo_copy (ba_assemble.hip.h).
 //
 // Solve chain (HipSchur::solve_async), the default first and the switch of ba_switches.h that selects each alternative:
 //   1. band pack, factorisation         ba_band_part.hip.h     k_band_pack, k_part_cholesky: the interior solves read their right-hand sides from the
@@ -56,6 +57,7 @@
 #include "ba_wave.hip.h"
 #include "ba_assemble_win.hip.h"
 #include "ba_assemble.hip.h"
+#include "ba_landmark.hip.h"
 #include "ba_band_generic.hip.h"
 #include "ba_band_part.hip.h"
 #include "ba_sep.hip.h"

@@ -562,6 +562,8 @@ struct HipSchur {
     // mvus_ba_set_position_priors: the priors' rows are added behind every assembly, whatever produced the Jacobian -- at the point the fused
     // kernel linearised, else the one the stored Jacobian was evaluated at; a handle without active priors launches nothing here
     if (be.prior_active > 0) be.prior_normal_equations(ne, x_fused ? x_fused : be.jac_x);
+    // mvus_ba_set_landmarks: the same on the camera side (A, gc), in front of the freeze pass, so held parameters stay held
+    if (be.lm_active > 0) be.landmark_normal_equations(ne, x_fused ? x_fused : be.jac_x);
     // mvus_ba_set_frozen: every assembly -- window-major, detection-major, robust, the speculative one (the bound set is the one just
     // written) -- is followed by the freeze pass; a handle without a mask launches nothing here
     if (be.frozen_count > 0) {
@@ -593,14 +595,21 @@ struct HipSchur {
   // other last bits.  A handle with neither a mask nor active priors assembles on every call, as always.
   void assemble_held(BE&) {
     const bool fused = be.held_analytic_at_xcur && use_win && !sw.ne_from_j;
-    const BlocksTag want{be.frozen_count > 0, fused, be.prior_active > 0 ? be.prior_gen : 0};
+    const BlocksTag want{be.frozen_count > 0, fused, be.prior_active > 0 ? be.prior_gen : 0, be.lm_active > 0 ? be.lm_gen : 0};
     if (be.mem.blocks_reusable(want)) {
       const BlocksTag& held = be.mem.held_blocks();
       if (held.prior_gen == 0 && want.prior_gen != 0) {
         be.prior_normal_equations(ne, fused ? be.x_cur : be.jac_x);
         diag_pending = true;
       }
-      if (!held.frozen && want.frozen) {
+      // (the landmarks' pass writes A and gc, which the freeze pass fixes -- unlike the priors', which stays on the spline side: where it goes
+      // on top of blocks that are frozen already, the freeze pass, idempotent, runs again behind it)
+      const bool landmarks_on_top = held.landmark_gen == 0 && want.landmark_gen != 0;
+      if (landmarks_on_top) {
+        be.landmark_normal_equations(ne, fused ? be.x_cur : be.jac_x);
+        diag_pending = true;
+      }
+      if (want.frozen && (!held.frozen || landmarks_on_top)) {
         hipLaunchKernelGGL(k_freeze_ne, dim3((unsigned)be.frozen_count), dim3(kFreezeThreads), 0, be.stream, ne, (const int32_t*)be.frozen_idx, be.frozen_count);
         MVUS_HIP(hipGetLastError());
         diag_pending = true;

@@ -197,7 +197,8 @@ def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output
     """main.py:18-93 from the config.json at ``path`` (the reference's schema; ``create_scene``): every stage through
     ``StageTimer`` -- create_scene, cut_detection, init_alpha, time_shift, detection_to_global, init_traj(error=thres_Fmatix),
     traj_to_spline, the incremental loop, spline_to_traj; with ``settings['ba_position_priors']`` and a position log
-    (``path_position_priors``) ``Scene.align_to_position_priors`` and one final LM BA over all cameras that carries the priors; ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true, ``Scene.ba_detection_covariance`` (which then serves both) when ``settings['ba_detection_covariance']`` is; ``Scene.kinematics`` (stage 'kinematics') when
+    (``path_position_priors``) ``Scene.align_to_position_priors`` and one final LM BA over all cameras that carries the priors; with ``settings['ba_landmarks']`` and the two
+    landmark files (``path_landmarks``, ``path_landmark_observations``) ``Scene.align_to_landmarks`` and that final BA with the landmarks (and the priors, when both are configured); ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true, ``Scene.ba_detection_covariance`` (which then serves both) when ``settings['ba_detection_covariance']`` is; ``Scene.kinematics`` (stage 'kinematics') when
     ``settings['ba_kinematics']`` is true; ``align_gt`` when the config gives ground truth; the Scene pickled to
     ``settings['path_output']`` when ``output`` and that key is set.  Returns (Scene, StageTimer)."""
     from .reconstruction import common
@@ -211,12 +212,25 @@ def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output
     timer.run('init_traj', 2, flight.init_traj, error=st.get('thres_Fmatix', 10))
     timer.run('traj_to_spline', 2, flight.traj_to_spline, smooth_factor=st['smooth_factor'])
     priors = flight.ba_position_priors()          # (validated before the loop; None: off, or no priors given)
+    marks = flight.ba_landmarks()                 # (likewise; None: off, or no landmarks given)
     held, flight.position_priors = flight.position_priors, None      # the loop runs exactly as without them: its BAs stay gauge-free
+    held_marks, flight.landmark_observations = flight.landmark_observations, None      # (register_camera in the loop is served: the scene holds no clicks meanwhile)
     try:
         incremental_reconstruction(flight, max_iter=max_iter, verbose=verbose, timer=timer)
     finally:
         flight.position_priors = held
-    if priors is not None:
+        flight.landmark_observations = held_marks
+    if marks is not None:
+        # settings['ba_landmarks']: into the surveyed frame by the similarity that takes the triangulated landmarks onto their surveyed
+        # positions, then one LM BA over all cameras with the clicks as observations (and the position priors, when both are configured);
+        # the trajectory, the covariance and the kinematics below are in that frame
+        num = flight.numCam if flight.find_order else len(flight.sequence)
+        s_, _, _, rms = timer.run('align_to_landmarks', num, flight.align_to_landmarks)
+        print('landmarks: similarity of scale %.6g onto the surveyed positions, rms %.4g' % (s_, rms))
+        timer.run('BA', num, flight.BA, num, max_iter=max_iter, rs=st['rolling_shutter'], motion_reg=st['motion_reg'],
+                  motion_weights=st['motion_weights'], rs_bounds=st['rs_bounds'])
+        timer.run('spline_to_traj', num, flight.spline_to_traj, sampling_rate=1)
+    elif priors is not None:
         # settings['ba_position_priors']: into the surveyed frame by the similarity that fits the spline to the priors, then one LM BA over all
         # cameras with the priors as observations; the trajectory, the covariance and the kinematics below are in that frame
         num = flight.numCam if flight.find_order else len(flight.sequence)

@@ -47,6 +47,12 @@ Extra ``settings`` keys (all optional; a reference ``config.json`` has none of t
                detection the signed residual, the 1-sigma ellipse of the fitted detection and the studentised residual.  DEFAULT False.
 ``ba_kinematics`` True: ``reconstruct_from_config`` calls ``Scene.kinematics`` after ``spline_to_traj`` (after ``Scene.ba_covariance``, with its band, when
                ``ba_covariance`` is on too) and the output pickle carries its dict.  DEFAULT False: nothing changes.
+``ba_landmarks`` True with 'lm': ``Scene.landmarks`` (3, L) -- surveyed static points -- and ``Scene.landmark_observations`` (6, K): camera id,
+               landmark, u, v, sigma_u, sigma_v -- enter ``Scene.BA`` as observations (``mvus_ba_set_landmarks``): two rows per click that
+               involve the clicked camera only and fix the similarity gauge, scale included.  ``reconstruct_from_config`` runs the
+               incremental loop as without them, then moves the result into the surveyed frame (``Scene.align_to_landmarks``) and ends
+               with one LM BA over all cameras that carries them.  Not with 'trf' (ValueError); a problem the wide-band policy above
+               would hand to TRF raises; ``register_camera`` raises while the setting is on and the scene holds landmarks.  DEFAULT false.
 ``ba_position_priors`` True with 'lm': ``Scene.position_priors`` -- surveyed positions (a GPS / RTK log) as a (7, K) array of t, x, y, z, sigma_x,
                sigma_y, sigma_z on the spline's timeline -- enter ``Scene.BA`` as observations (``mvus_ba_set_position_priors``): three
                non-collinear ones fix the similarity gauge, and the trajectory, the poses and their covariance come out in the surveyed
@@ -220,6 +226,8 @@ class Scene:
         self.find_order = True
         self._ba_handle = None      # GPU handle kept between BA -> remove_outliers -> BA (main.py:49-62)
         self._ba_key = None
+        self.landmarks = None          # (3, L) surveyed static points, or None (settings['ba_landmarks'])
+        self.landmark_observations = None      # (6, K): camera id, landmark, u, v, sigma_u, sigma_v
         self.position_priors = None    # (7, K): t, x, y, z, sigma_x, sigma_y, sigma_z of surveyed positions, or None (settings['ba_position_priors'])
 
     def __getstate__(self):         # the output pickle (main.py:93) carries data only
@@ -494,6 +502,7 @@ class Scene:
                 h.set_frozen(mask)
         priors = self.ba_position_priors()
         self._apply_position_priors(h, priors)
+        self._apply_landmarks(h, self.ba_landmarks(cams))
         opts = _ba._lib.default_opts(solver, jac_mode, max_iter)
         opts.lm_lambda_min = float(st.get('ba_lambda_min', opts.lm_lambda_min))
         opts.lm_trust_radius = float(st.get('ba_trust_radius', opts.lm_trust_radius))
@@ -517,6 +526,10 @@ class Scene:
                 # nor position priors: never solved with them dropped
                 raise _ba.UnsupportedBySolver("settings['ba_position_priors'] needs the LM solver, which does not take this problem (%s); the fallback "
                                               "to ba_solver=trf would drop the priors -- set ba_lm_wide_band: 'lm' or ba_position_priors: false" % (e,)) from e
+            if h.num_landmark_rows:
+                # nor landmarks
+                raise _ba.UnsupportedBySolver("settings['ba_landmarks'] needs the LM solver, which does not take this problem (%s); the fallback "
+                                              "to ba_solver=trf would drop the landmarks -- set ba_lm_wide_band: 'lm' or ba_landmarks: false" % (e,)) from e
             # LM + Schur keeps the spline block as a band of at most sixteen 3x3 blocks (MVUS_E_UNSUPPORTED beyond; FITPACK knots far
             # below one frame apart make the motion rows reach further).  The other GPU solver has no such limit: same analytic
             # Jacobian, TRF + LSMR instead of the normal equations.  Said aloud and recorded in the result, not silently.
@@ -527,6 +540,7 @@ class Scene:
         res.num_frozen = h.num_frozen
         res.num_position_priors = h.num_position_priors
         res.num_active_position_priors = h.num_active_position_priors
+        res.num_landmark_observations = h.num_landmark_observations
         alpha, beta, rs_new, cam_states, coefs = _problem.unpack_x(prob, res.x)
         self.alpha[cams], self.beta[cams], self.rs[cams] = alpha, beta, rs_new
         for k, i in enumerate(cams):
@@ -565,7 +579,102 @@ class Scene:
         self.ba_register_enabled()           # (and ba_register / ba_register_beta_search)
         self.ba_register_beta_search()
         self.ba_position_priors()            # (and ba_position_priors / Scene.position_priors)
+        self.ba_landmarks()                  # (and ba_landmarks / Scene.landmarks / Scene.landmark_observations)
         return solver, modes[jac]
+
+    def ba_landmarks(self, cams=None):
+        """(X (3, L), cam (K,), point (K,), uv (2, K), sigma (2, K)) when settings['ba_landmarks'] is true and the scene holds landmarks and
+        observations, else None.  Validated on the host, before any GPU call: the flag is a bool, the arrays are finite with positive sigmas
+        (inf = that axis unknown) and landmark indices inside [0, L), and the solver must be 'lm'.  ``cams``: the BA's camera set --
+        observations of other cameras are left out and the camera id becomes the index in ``cams`` (None: ids as they are)."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        v = st.get('ba_landmarks', False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("settings['ba_landmarks'] must be true or false, not %r" % (v,))
+        if not v:
+            return None
+        if st.get('ba_solver', 'trf') != 'lm':
+            raise ValueError("settings['ba_landmarks'] needs settings['ba_solver'] = 'lm' (the TRF + LSMR solver takes no landmarks), "
+                             "not %r" % (st.get('ba_solver', 'trf'),))
+        X, ob = getattr(self, 'landmarks', None), getattr(self, 'landmark_observations', None)
+        if X is None or ob is None:
+            return None
+        X, ob = check_landmarks(X, ob, 'Scene.landmarks')
+        cam = ob[0].astype(np.int64)
+        if cams is not None:
+            index = {int(c): k for k, c in enumerate(cams)}
+            keep = np.array([int(c) in index for c in cam], dtype=bool)
+            ob, cam = ob[:, keep], np.array([index[int(c)] for c in cam[keep]], dtype=np.int64)
+        if ob.shape[1] == 0:
+            return None
+        return X.copy(), cam.astype(np.int32), ob[1].astype(np.int32), ob[2:4].copy(), ob[4:6].copy()
+
+    @staticmethod
+    def _apply_landmarks(h, lm):
+        """The landmarks in force on the handle are ``lm`` (None: none), set only when they differ, as with the priors."""
+        if lm is None:
+            if h.num_landmark_observations:
+                h.set_landmarks(None, None, None, None, None)
+                h._landmarks = None
+            return
+        cur = getattr(h, '_landmarks', None)
+        if cur is not None and h.num_landmark_observations == lm[1].size and all(np.array_equal(a, b) for a, b in zip(cur, lm)):
+            return
+        h.set_landmarks(*lm)
+        h._landmarks = lm
+
+    def triangulate_landmarks(self):
+        """(ids, Y (3, len(ids))): every landmark seen by at least two cameras that have a pose, triangulated from the current cameras by a
+        multi-view DLT on the host (undistorted, normalised image points; L is tens).  Whatever the settings say."""
+        X, ob = getattr(self, 'landmarks', None), getattr(self, 'landmark_observations', None)
+        if X is None or ob is None:
+            return np.empty(0, dtype=np.int64), np.empty((3, 0))
+        X, ob = check_landmarks(X, ob, 'Scene.landmarks')
+        st = self.settings if isinstance(self.settings, dict) else {}
+        undist = bool(st.get('undist_points', False))
+        ids, Y = [], []
+        for l in range(X.shape[1]):
+            rows, seen = [], set()
+            for k in np.nonzero(ob[1].astype(np.int64) == l)[0]:
+                c = int(ob[0, k])
+                if not 0 <= c < len(self.cameras):
+                    continue
+                cam = self.cameras[c]
+                if getattr(cam, 'R', None) is None or getattr(cam, 't', None) is None or cam.K is None:
+                    continue
+                K = np.asarray(cam.K, dtype=np.float64)
+                xn, yn = (ob[2, k] - K[0, 2]) / K[0, 0], (ob[3, k] - K[1, 2]) / K[1, 1]
+                if undist and cam.d is not None:
+                    xn, yn = _undistort_normalised(xn, yn, np.ravel(np.asarray(cam.d, dtype=np.float64)))
+                Pm = np.hstack((np.asarray(cam.R, dtype=np.float64), np.ravel(np.asarray(cam.t, dtype=np.float64))[:, None]))
+                rows += [xn * Pm[2] - Pm[0], yn * Pm[2] - Pm[1]]
+                seen.add(c)
+            if len(seen) < 2:
+                continue
+            A = np.array(rows)
+            A /= np.linalg.norm(A, axis=1, keepdims=True)
+            v = np.linalg.svd(A)[2][-1]
+            if v[3] == 0:
+                continue
+            ids.append(l)
+            Y.append(v[:3] / v[3])
+        return np.array(ids, dtype=np.int64), (np.array(Y).T if Y else np.empty((3, 0)))
+
+    def align_to_landmarks(self):
+        """The similarity (Umeyama) that takes the landmarks as the current cameras triangulate them (``triangulate_landmarks``) onto their
+        surveyed positions, applied to the scene (``apply_similarity``); returns (s, R, T, rms).  Needs at least three such landmarks that
+        are not collinear -- the rule of ``align_to_position_priors`` -- else ValueError."""
+        ids, Y = self.triangulate_landmarks()
+        if ids.size < 3:
+            raise ValueError('align_to_landmarks: %d landmarks seen by at least two placed cameras, at least 3 are needed' % ids.size)
+        Xs = np.asarray(self.landmarks, dtype=np.float64)[:, ids]
+        sv = np.linalg.svd(Xs - Xs.mean(axis=1, keepdims=True), compute_uv=False)
+        if not sv[1] > 1e-6 * sv[0]:
+            raise ValueError('align_to_landmarks: the landmarks are collinear (singular values %s): the similarity is not determined' % (sv,))
+        s, R, T = umeyama_similarity(Y, Xs)
+        rms = float(np.sqrt(np.mean(np.sum((s * (R @ Y) + T[:, None] - Xs) ** 2, axis=0))))
+        self.apply_similarity(s, R, T)
+        return s, R, T, rms
 
     def ba_position_priors(self):
         """(t (K,), P (3, K), sigma (3, K)) when settings['ba_position_priors'] is true and ``self.position_priors`` holds priors, else
@@ -729,6 +838,10 @@ class Scene:
         loss gives way to gross outliers that PnP + RANSAC ignored (a robust ``ba_loss`` is the remedy, and then the winner is kept)."""
         cam_id = int(cam_id)
         st = self.settings if isinstance(self.settings, dict) else {}
+        if self.ba_landmarks() is not None:          # (the setting is on AND the scene holds landmarks and clicks)
+            from .. import ba as _ba
+            raise _ba.UnsupportedBySolver("register_camera: settings['ba_landmarks'] is on -- the per-camera problem holds no landmark rows and "
+                                          "would drop exactly the ones that involve this camera")
         calib = bool(st.get('opt_calib', False))
         hold = tuple(hold) if hold is not None else ()
         for name in hold:
@@ -876,6 +989,7 @@ class Scene:
         if not np.array_equal(mask, cur if cur is not None else np.zeros(mask.size, dtype=bool)):
             h.set_frozen(mask)
         self._apply_position_priors(h, self.ba_position_priors())
+        self._apply_landmarks(h, self.ba_landmarks(cams))
         return h, prob, x
 
     def _store_covariance(self, cv, cams, prob, t):
@@ -1231,6 +1345,74 @@ def umeyama_similarity(X, Y):
     return s, R, T
 
 
+def _undistort_normalised(x0, y0, d):
+    """cv2.undistortPoints on normalised coordinates (five fixed-point iterations), host side"""
+    k1, k2, p1, p2, k3 = (list(d) + [0.0] * 5)[:5]
+    x, y = x0, y0
+    for _ in range(5):
+        r2 = x * x + y * y
+        ic = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        if ic < 0:
+            return x0, y0
+        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (x0 - dx) * ic, (y0 - dy) * ic
+    return x, y
+
+
+def check_landmarks(X, ob, what='landmarks'):
+    """((3, L) landmarks, (6, K) observations: camera id, landmark, u, v, sigma_u, sigma_v), validated: finite positions and pixels, whole
+    non-negative camera ids, landmark indices inside [0, L), sigmas positive (inf allowed)."""
+    X, ob = np.asarray(X, dtype=np.float64), np.asarray(ob, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != 3:
+        raise ValueError('%s must be a (3, L) array, not shape %s' % (what, X.shape))
+    if ob.ndim != 2 or ob.shape[0] != 6:
+        raise ValueError('%s: the observations must be a (6, K) array of camera, landmark, u, v, sigma_u, sigma_v, not shape %s' % (what, ob.shape))
+    if not np.all(np.isfinite(X)) or not np.all(np.isfinite(ob[:4])):
+        raise ValueError('%s: a position, an index or a pixel is not finite' % what)
+    if np.any(ob[:2] != np.floor(ob[:2])) or np.any(ob[0] < 0) or np.any(ob[1] < 0) or np.any(ob[1] >= X.shape[1]):
+        raise ValueError('%s: camera ids must be whole and >= 0, landmark indices whole and inside [0, %d)' % (what, X.shape[1]))
+    if np.any(np.isnan(ob[4:])) or np.any(ob[4:] <= 0):
+        raise ValueError('%s: sigma must be positive (inf leaves an axis out)' % what)
+    return X, ob
+
+
+def load_landmarks(path_points, path_observations, default_sigma=None):
+    """Two text files (``#`` comments): ``id x y z`` per landmark and ``camera id u v [sigma_u sigma_v]`` per click -> ((3, L), (6, K)) with the
+    ids replaced by the landmark's position in the first file.  Clicks without sigma columns take ``default_sigma`` (a positive number, or
+    two of them)."""
+    try:
+        a = np.loadtxt(path_points, dtype=np.float64, ndmin=2)
+        b = np.loadtxt(path_observations, dtype=np.float64, ndmin=2)
+    except ValueError as e:
+        raise ValueError('landmarks %s / %s: %s' % (path_points, path_observations, e)) from None
+    if a.shape[0] and a.shape[1] != 4:
+        raise ValueError('landmarks %s: %d columns, expected id x y z' % (path_points, a.shape[1]))
+    a = a.reshape(-1, 4)
+    ids = a[:, 0]
+    if np.any(ids != np.floor(ids)) or np.unique(ids).size != ids.size:
+        raise ValueError('landmarks %s: ids must be whole numbers, each once' % path_points)
+    if b.shape[0] == 0:
+        return a[:, 1:4].T.copy(), np.empty((6, 0))
+    if b.shape[1] == 4:
+        if default_sigma is None:
+            raise ValueError("landmark observations %s: columns camera id u v only -- give sigma_u sigma_v columns or 'landmark_sigma'" % path_observations)
+        sg = np.asarray(default_sigma, dtype=np.float64)
+        if sg.shape not in ((), (2,)) or isinstance(default_sigma, bool):
+            raise ValueError("'landmark_sigma' must be a positive number or two of them, not %r" % (default_sigma,))
+        b = np.hstack((b, np.broadcast_to(sg, (b.shape[0], 2))))
+    elif b.shape[1] != 6:
+        raise ValueError('landmark observations %s: %d columns, expected camera id u v [sigma_u sigma_v]' % (path_observations, b.shape[1]))
+    where = {int(i): k for k, i in enumerate(ids)}
+    unknown = [int(i) for i in b[:, 1] if i != np.floor(i) or int(i) not in where]
+    if unknown:
+        raise ValueError('landmark observations %s: ids %s are not in %s' % (path_observations, sorted(set(unknown)), path_points))
+    ob = b.T.copy()
+    ob[1] = [where[int(i)] for i in b[:, 1]]
+    X, ob = check_landmarks(a[:, 1:4].T.copy(), ob, 'landmarks %s' % path_points)
+    return X, ob
+
+
 def check_position_priors(pp, what='position priors'):
     """A (7, K) float array of t, x, y, z, sigma_x, sigma_y, sigma_z, validated: finite t and positions, sigmas positive (inf allowed)."""
     pp = np.asarray(pp, dtype=np.float64)
@@ -1304,5 +1486,9 @@ def create_scene(path_input):
         # surveyed positions (GPS / RTK log): t x y z [sigma_x sigma_y sigma_z] per line, t on the reference camera's frame clock
         flight.position_priors = load_position_priors(opt['path_position_priors'], opt.get('position_prior_sigma'))
     flight.ba_position_priors()              # (settings['ba_position_priors'] validated here, before any GPU work)
+    if opt.get('path_landmarks') and opt.get('path_landmark_observations'):
+        # surveyed static points: id x y z per line, and their clicks: camera id u v [sigma_u sigma_v] per line
+        flight.landmarks, flight.landmark_observations = load_landmarks(opt['path_landmarks'], opt['path_landmark_observations'], opt.get('landmark_sigma'))
+    flight.ba_landmarks()                    # (settings['ba_landmarks'] likewise)
     print('Input data are loaded successfully, a scene is created.\n')
     return flight

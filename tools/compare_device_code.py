@@ -6,7 +6,7 @@
 
 Per symbol: the text of every @function symbol from its label to its .Lfunc_end, and every .amdhsa_kernel ... .end_amdhsa_kernel
 descriptor.  Only the numbers that say where in the module a function sits are normalised (.LBB<n>_, .Lfunc_begin/end<n>, .Ltmp<n>,
-.LJTI<n>_, and BB<n>_ where a loop comment repeats a label), so a move that reorders the kernels compares equal and nothing else does.  Prints one line; exit status 1 on any
+.LJTI<n>_, BB<n>_ where a loop comment repeats a label, and the padding between a label and its comment), so a move that reorders the kernels compares equal and nothing else does.  Prints one line; exit status 1 on any
 difference.  Keep the .s files outside the repository.
 """
 import re
@@ -14,6 +14,7 @@ import sys
 
 POSITION = re.compile(r"\.(LBB|Lfunc_begin|Lfunc_end|Ltmp|LJTI)\d+")
 LOOP_NOTE = re.compile(r"\bBB\d+(?=_\d)")      # the same label number in the assembler's loop comments ("in Loop: Header=BB32_3")
+LABEL_PAD = re.compile(r"^(\.LBB#_\d+:) +;", re.M)      # the comment behind a label starts at a fixed column: a function number that gains a digit moves it
 
 
 def symbols(path):
@@ -25,7 +26,7 @@ def symbols(path):
     for name in functions:
         i = start[name]
         j = next(k for k in range(i, len(lines)) if lines[k].startswith(".Lfunc_end"))
-        out[name] = LOOP_NOTE.sub("BB#", POSITION.sub(r".\1#", "\n".join(lines[i:j + 1])))
+        out[name] = LABEL_PAD.sub(r"\1 ;", LOOP_NOTE.sub("BB#", POSITION.sub(r".\1#", "\n".join(lines[i:j + 1]))))
     i = 0
     while i < len(lines):
         m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", lines[i])
