@@ -147,7 +147,7 @@ void mvus_default_opts(mvus_solve_opts* opts);
  * sizeof(mvus_result), sizeof(mvus_problem) as this library was compiled (any pointer may be NULL) and returns MVUS_ABI_VERSION.  A
  * binding asserts these against its own struct definitions at load time -- mvus_solve_opts has grown over the rounds (lm_lambda_min,
  * lm_trust_radius) and a stale stub would otherwise hand the library a short buffer.  The version is raised whenever a struct or an
- * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance, mvus_ba_set_position_priors, mvus_ba_detection_covariance, mvus_ba_set_landmarks) does not raise
+ * EXISTING prototype of this header changes; an entry point that is only added (mvus_ba_set_frozen, mvus_ba_num_frozen, mvus_ba_covariance, mvus_ba_set_position_priors, mvus_ba_detection_covariance, mvus_ba_set_landmarks, mvus_triangulate_cov, mvus_spline_fit_open_w, mvus_spline_smooth_w, mvus_spline_fit_normal_w, mvus_spline_fit_residual_w) does not raise
  * it -- a binding that needs one finds it missing at load time.  Stateless, no device is touched.  No reference counterpart (the reference has no FFI). */
 #define MVUS_ABI_VERSION 8
 int32_t mvus_abi_sizes(int32_t* solve_opts_size, int32_t* result_size, int32_t* problem_size);
@@ -529,6 +529,19 @@ int mvus_ba_set_x(mvus_ba* h, const double* x);
 int mvus_triangulate(int32_t device, int64_t N, const double* x1, const double* x2, const double* P1, const double* P2,
                      double* X, double* err1, double* err2);
 
+/* mvus_triangulate with the covariance of every point.  Arguments, layouts and the bits of X, err1, err2 as there (the same Jacobi SVD, one
+ * lane per pair, in k_triangulate_cov).  cov[6*N], component-major xx(N) xy(N) xz(N) yy(N) yz(N) zz(N): the Gauss-Newton covariance
+ * (A^T A)^-1 of the point at the returned X, A the four rows (P_c[r,:3] - x_r P_c[2,:3]) / (z_c sigma_c), r = 0, 1, c = 1, 2, with (x_0, x_1)
+ * the reprojection of X in camera c, z_c its third homogeneous component and sigma_c the pixel noise (1-sigma, isotropic) of camera c; the
+ * 3x3 inverse by Cholesky in registers.  To first order this is the covariance of the point of least reprojection error; the linear
+ * triangulation is close to that point, not equal to it (tests/test_gpu_triangulate_cov.py measures how close).  All six entries of a pair are
+ * NaN when a Cholesky pivot is at most 1e-14 of its diagonal entry (no parallax), X is not finite, or z_c <= 0 in either camera.
+ * Not offered: a full 2x2 pixel covariance per detection, and the covariance of anything but the point (the cameras are taken as exact).
+ * MVUS_E_INVALID, before the device is touched: sigma1 or sigma2 not finite or <= 0; cov == NULL (mvus_triangulate is that call); what
+ * mvus_triangulate refuses.  Stateless; no CPU fallback.  No reference counterpart. */
+int mvus_triangulate_cov(int32_t device, int64_t N, const double* x1, const double* x2, const double* P1, const double* P2, double sigma1, double sigma2,
+                         double* X, double* cov, double* err1, double* err2);
+
 /* Scene.spline_to_traj (common.py:273-301): evaluate the S trajectory splines at nt timestamps.  interval: [2*S] row-major
  * spline['int'] (starts then ends); knot_offsets [S+1] / knots: concatenated spline['tck'][s][0]; coefs: concatenated
  * spline['tck'][s][1] (cx(n_s) cy(n_s) cz(n_s) per spline).  which[nt] receives the interval each timestamp belongs to
@@ -595,6 +608,23 @@ int mvus_spline_fit_open(int32_t device, int64_t m, const double* u, const doubl
 int mvus_spline_fit_smooth(mvus_spline_fit* fit, double s, int32_t* n_out, double* t_out, double* c_out, double* fp_out, int32_t* ier_out);
 void mvus_spline_fit_close(mvus_spline_fit* fit);
 
+/* The same fit with splprep's w: scipy.interpolate.splprep(X, w=w, u=u, s=s, k=3), one weight per sample (the reference never passes
+ * one; Scene.traj_to_spline does when settings['traj_weights'] is set, with w ~ 1 / sigma of the triangulated point).  fppara reads w in two
+ * places and so does the fit: the row of sample i in the least-squares system is w_i h with right-hand side w_i X_i (k_fit_blocks_w), and its
+ * residual is |w_i (s(u_i) - X_i)|^2 (k_fit_residual_w), which is what the knot search, *fp_out and the comparison with s see.  The knot search
+ * itself, fpdisc, fprati, the penalty and both band solvers are those of the unweighted fit; so is the double-double escalation, with two
+ * additions for weighted fits: double-double from the pass on with more than half as many coefficients as samples (2 ncoef > m), and in
+ * those passes *fp of a least-squares pass from its factorisation (|w x|^2 - |y|^2, as fppara forms it) instead of from coefficients
+ * rounded to fp64.  Such a pass solves its system in one chain of ncoef rows, 4.8 us a row: 1.6 ms at 340 coefficients, 17 ms at 3 600;
+ * fits of oversampled trajectories (a few hundred knots for 1e5 samples) never get there and keep the partitioned solver.  w[m] finite and
+ * strictly positive (scipy's condition), else MVUS_E_INVALID.  w == NULL: the unweighted session / fit, bit for bit, on the unweighted
+ * kernels.  mvus_spline_fit_smooth and mvus_spline_fit_close serve both kinds of session.
+ * Not offered: a 3x3 weight per sample (FITPACK's w is one scalar per sample), and weights in the fallback for parts of fewer than four
+ * samples (mvus_amd.spline.linear_fit_as_cubic, a host restatement). */
+int mvus_spline_fit_open_w(int32_t device, int64_t m, const double* u, const double* X, const double* w, mvus_spline_fit** out);
+int mvus_spline_smooth_w(int32_t device, int64_t m, const double* u, const double* X, const double* w, double s, int32_t* n_out, double* t_out,
+                         double* c_out, double* fp_out, int32_t* ier_out);
+
 /* The banded solvers of that fit on a system handed in: inspection hooks for k_band_solve, k_band_solve_parts and k_band_diag_sum
  * (spline_fit.hip.h), as mvus_ba_lm_step is for the Schur chain.  No reference counterpart.
  *   G5[5*n], BtB[5*n]: the kernels' lower-band layout, M(j, j - w) at 5 j + w, w = 0..4; entries with j - w < 0 must be 0.
@@ -641,6 +671,14 @@ int mvus_spline_fit_normal(int32_t device, int64_t m, const double* u, const dou
 int mvus_spline_fit_penalty(int32_t device, int32_t ncoef, int32_t n8, const double* b, int32_t precise, double* BtB_out, double* BtB_lo_out);
 int mvus_spline_fit_residual(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, const double* c, int32_t slices,
                              double* term_out, double* fp_out, double* fpint_out);
+/* The same two passes of a weighted fit (mvus_spline_fit_open_w), w[m] after X: the normal equations of the rows w_i h with right-hand sides
+ * w_i X_i (k_fit_blocks_w; q_out stays the unweighted basis, as FITPACK stores it), and term_out[m] = |w_i (s(u_i) - X_i)|^2 (k_fit_residual_w).
+ * w == NULL: the calls above, bit for bit.  MVUS_E_INVALID also for a weight that is not finite or not > 0. */
+int mvus_spline_fit_normal_w(int32_t device, int64_t m, const double* u, const double* X, const double* w, int32_t n, const double* t, int32_t precise,
+                             int32_t slices, int32_t parts, int32_t* span_out, double* q_out, int64_t* first_out, double* G5_out, double* G5_lo_out,
+                             double* rhs_out, double* rhs_lo_out, double* c_out, double* stats_out, int32_t* fail_out);
+int mvus_spline_fit_residual_w(int32_t device, int64_t m, const double* u, const double* X, const double* w, int32_t n, const double* t, const double* c,
+                               int32_t slices, double* term_out, double* fp_out, double* fpint_out);
 
 /* Scene.get_camera_pose's cv2.solvePnPRansac(objectPoints, imagePoints, K, d, reprojectionError=error) (common.py:744; OpenCV is
  * a third-party dependency absent from this image: parity unpinned, see pnp.hip.h).  X[3*N] object points (x(N) y(N) z(N)),

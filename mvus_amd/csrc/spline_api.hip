@@ -49,22 +49,25 @@ static bool fit_band_solve(hipStream_t st, FitWork<T>& w, int ncoef, const T* Mb
   return fit_band_solve<HB, T>(st, w, ncoef, band_parts(ncoef, HB, band_parts_min()), Mband, cd, out, fail);
 }
 // least-squares spline on the current knots: normal equations from the span blocks, banded Cholesky, coefficients -> cd
-// (nslice slices per span -- the fit passes fit_slices(nrint) -- and the partition bp of the solve: band_parts(ncoef, 3, band_parts_min()))
+// (nslice slices per span -- the fit passes fit_slices(nrint) -- and the partition bp of the solve: band_parts(ncoef, 3, band_parts_min());
+// wt: the weights of a weighted fit on the device, or NULL -- then the kernel that reads none)
 template <class T>
-static bool fit_lsq_pass(hipStream_t st, FitWork<T>& w, long long m, const long long* first, const double* q, const double* dX, int ncoef, int nrint,
-                         int nslice, const BandParts& bp, double* cd, double* out, int* fail) {
+static bool fit_lsq_pass(hipStream_t st, FitWork<T>& w, long long m, const long long* first, const double* q, const double* dX, const double* wt, int ncoef,
+                         int nrint, int nslice, const BandParts& bp, double* cd, double* out, int* fail) {
   constexpr int NT = sizeof(T) == sizeof(double) ? 256 : 64;
-  hipLaunchKernelGGL((k_fit_blocks<T, NT>), dim3(nrint, nslice), dim3(NT), 0, st, m, first, q, dX, w.SB);
+  if (wt) hipLaunchKernelGGL((k_fit_blocks_w<T, NT>), dim3(nrint, nslice), dim3(NT), 0, st, m, first, q, dX, wt, w.SB);
+  else hipLaunchKernelGGL((k_fit_blocks<T, NT>), dim3(nrint, nslice), dim3(NT), 0, st, m, first, q, dX, w.SB);
   if (nslice > 1) hipLaunchKernelGGL(k_fit_slice_sum<T>, fit_blocks((long long)nrint * kFitBlk), dim3(256), 0, st, (long long)nrint * kFitBlk, nslice, w.SB);
   hipLaunchKernelGGL(k_fit_band<T>, fit_blocks(ncoef), dim3(256), 0, st, ncoef, nrint, w.SB, w.G5, w.rhs, bp, w.Lf, w.yw);
   w.penalty = false;
   return fit_band_solve<3, T>(st, w, ncoef, bp, w.G5, cd, out, fail);
 }
 // c -> the squared residual of every sample (term), their total f_p (out[1]) and, with `spans`, the per-span sums (out[4 + sp]) in
-// nslice slices per span (the fit passes fit_slices(nspan))
-static void fit_residual_pass(hipStream_t st, long long m, int ncoef, const int32_t* span, const double* q, const double* dX, const double* cd, double* term,
-                              double* tot_part, double* out, bool spans, int nspan, int nslice, const long long* first, double* fp_part) {
-  hipLaunchKernelGGL(k_fit_residual, fit_blocks(m), dim3(256), 0, st, m, ncoef, span, q, dX, cd, term);
+// nslice slices per span (the fit passes fit_slices(nspan)); wt as in fit_lsq_pass: the residuals are then the weighted ones
+static void fit_residual_pass(hipStream_t st, long long m, int ncoef, const int32_t* span, const double* q, const double* dX, const double* wt, const double* cd,
+                              double* term, double* tot_part, double* out, bool spans, int nspan, int nslice, const long long* first, double* fp_part) {
+  if (wt) hipLaunchKernelGGL(k_fit_residual_w, fit_blocks(m), dim3(256), 0, st, m, ncoef, span, q, dX, wt, cd, term);
+  else hipLaunchKernelGGL(k_fit_residual, fit_blocks(m), dim3(256), 0, st, m, ncoef, span, q, dX, cd, term);
   if (m > kFitTotalOneStage) {                                    // two stages (still one fixed order)
     const int nbt = fit_total_parts(m);
     hipLaunchKernelGGL(k_fit_total_partial, dim3(nbt), dim3(256), 0, st, m, term, tot_part);
@@ -165,10 +168,17 @@ static void band_read(CallBuffers& cb, const dd* src, double* hi, double* lo, si
   MVUS_HIP(hipStreamSynchronize(cb.st));
   for (size_t i = 0; i < count; ++i) { hi[i] = stage[i].hi; if (lo) lo[i] = stage[i].lo; }
 }
+// what a weight vector must be (scipy's own condition on splprep's w); NULL: the unweighted fit
+static const char* const kFitWeightsWrong = "the weights must be finite and strictly positive";
+static bool fit_weights_ok(int64_t m, const double* w) {
+  if (w) for (int64_t i = 0; i < m; ++i) if (!std::isfinite(w[i]) || !(w[i] > 0.0)) return false;
+  return true;
+}
 // the checks the three share; slices: 0 the production rule, else exactly that many
-static bool fit_inspect_args_ok(const char* name, int64_t m, const double* u, const double* X, int32_t n, const double* t, int32_t slices) {
+static bool fit_inspect_args_ok(const char* name, int64_t m, const double* u, const double* X, const double* w, int32_t n, const double* t, int32_t slices) {
   if (const char* wrong = fit_samples_knots_wrong(m, u, n, t)) { g_create_error = std::string(name) + ": " + wrong; return false; }
   for (int64_t i = 0; i < 3 * m; ++i) if (!std::isfinite(X[i])) { g_create_error = std::string(name) + ": non-finite sample"; return false; }
+  if (!fit_weights_ok(m, w)) { g_create_error = std::string(name) + ": " + kFitWeightsWrong; return false; }
   if (slices != 0 && !fit_slices_legal(n - 7, slices)) {
     g_create_error = std::string(name) + ": slices must be 0 (the production rule) or 1..256 with spans x (slices - 1) <= 1536 and spans x slices <= 2048";
     return false;
@@ -177,27 +187,28 @@ static bool fit_inspect_args_ok(const char* name, int64_t m, const double* u, co
 }
 // samples and knots on the device, then what every pass of the fit starts with: k_fit_basis and k_fit_first
 struct FitInputs {
-  const double *du = nullptr, *dX = nullptr, *td = nullptr;
+  const double *du = nullptr, *dX = nullptr, *dw = nullptr, *td = nullptr;
   int32_t* span = nullptr;
   double* q = nullptr;
   long long* first = nullptr;
-  void upload(CallBuffers& cb, int64_t m, const double* u, const double* X, int n, const double* t) {
+  void upload(CallBuffers& cb, int64_t m, const double* u, const double* X, const double* w, int n, const double* t) {
     const int ncoef = n - 4, nspan = n - 7;
     du = cb.put(u, (size_t)m); dX = cb.put(X, 3 * (size_t)m); td = cb.put(t, (size_t)n);
+    if (w) dw = cb.put(w, (size_t)m);
     span = cb.get<int32_t>((size_t)m); q = cb.get<double>(4 * (size_t)m); first = cb.get<long long>((size_t)nspan + 1);
     hipLaunchKernelGGL(k_fit_basis, fit_blocks(m), dim3(256), 0, cb.st, (long long)m, du, td, ncoef, span, q);
     hipLaunchKernelGGL(k_fit_first, fit_blocks(nspan + 1), dim3(256), 0, cb.st, (long long)m, du, td, nspan, first);
   }
 };
 template <class T>
-static int fit_normal_run(int32_t device, int64_t m, const double* u, const double* X, int n, const double* t, int slices, const BandParts& bp, int32_t* span_out,
+static int fit_normal_run(int32_t device, int64_t m, const double* u, const double* X, const double* wt, int n, const double* t, int slices, const BandParts& bp, int32_t* span_out,
                           double* q_out, int64_t* first_out, double* G5_out, double* G5_lo_out, double* rhs_out, double* rhs_lo_out, double* c_out,
                           double* stats_out, int32_t* fail_out) {
   const int ncoef = n - 4, nspan = n - 7;
   CallBuffers cb;
   cb.open(device);
   FitInputs in;
-  in.upload(cb, m, u, X, n, t);
+  in.upload(cb, m, u, X, wt, n, t);
   FitWork<T> w;
   w.alloc(cb, (size_t)n);
   double* cd = cb.get<double>(3 * (size_t)ncoef);
@@ -207,7 +218,7 @@ static int fit_normal_run(int32_t device, int64_t m, const double* u, const doub
   const double out0[4] = {unset, unset, unset, unset};
   MVUS_HIP(hipMemcpyAsync(out, out0, sizeof(out0), hipMemcpyHostToDevice, cb.st));
   MVUS_HIP(hipMemsetAsync(fail, 0, sizeof(int), cb.st));
-  fit_lsq_pass<T>(cb.st, w, (long long)m, in.first, in.q, in.dX, ncoef, nspan, slices ? slices : fit_slices(nspan), bp, cd, out, fail);
+  fit_lsq_pass<T>(cb.st, w, (long long)m, in.first, in.q, in.dX, in.dw, ncoef, nspan, slices ? slices : fit_slices(nspan), bp, cd, out, fail);
   MVUS_HIP(hipGetLastError());
   int fh = 0;
   std::vector<long long> fh_first((size_t)nspan + 1);
@@ -430,14 +441,17 @@ int mvus_spline_lsq(int32_t device, int32_t num_knots, const double* knots, int6
   });
 }
 
-/* scipy.interpolate.splprep(X, u=u, s=s, k=3) on the GPU (spline_fit.hip.h): fppara's control flow here, every pass over the
+/* scipy.interpolate.splprep(X, w=w, u=u, s=s, k=3) on the GPU (spline_fit.hip.h): fppara's control flow here, every pass over the
  * samples and every banded solve on the device.  A SESSION holds the samples (checked and uploaded once) and the work arrays:
  * traj_to_spline's smooth_factor loop fits the same samples a dozen times with different s. */
 struct mvus_spline_fit {
   CallBuffers cb;
   int64_t m = 0;
   std::vector<double> hu;                                  // the timestamps on the host (fpknot places knots at samples)
-  const double *du = nullptr, *dX = nullptr;
+  const double *du = nullptr, *dX = nullptr, *dw = nullptr;      // dw: the weights of a weighted session, else NULL
+  dd* bb = nullptr;                                        // weighted session: |w x|^2 on the device (k_fit_wx2), summed when first needed
+  bool bb_ready = false;
+  double* fp_factor = nullptr;                             // ... and where that kernel leaves f_p
   int32_t* span = nullptr;
   double *q = nullptr, *term = nullptr, *tot_part = nullptr, *fp_part = nullptr;
   int* fail = nullptr;
@@ -447,11 +461,12 @@ struct mvus_spline_fit {
   FitWork<dd> w2;
   size_t cap = 0;
 };
-static int spline_fit_open_impl(mvus_spline_fit& S, int32_t device, int64_t m, const double* u, const double* X) {
+static int spline_fit_open_impl(mvus_spline_fit& S, int32_t device, int64_t m, const double* u, const double* X, const double* w) {
   constexpr int k = 3;
   if (m <= k || m > (1ll << 30) || !u || !X) { g_create_error = "spline_smooth: bad arguments (m > 3 samples, s > 0)"; return MVUS_E_INVALID; }
   for (int64_t i = 1; i < m; ++i) if (!(u[i] > u[i - 1])) { g_create_error = "spline_smooth: the timestamps must be strictly increasing"; return MVUS_E_INVALID; }
   for (int64_t i = 0; i < 3 * m; ++i) if (!std::isfinite(X[i])) { g_create_error = "spline_smooth: non-finite sample"; return MVUS_E_INVALID; }
+  if (!fit_weights_ok(m, w)) { g_create_error = std::string("spline_smooth: ") + kFitWeightsWrong; return MVUS_E_INVALID; }
   return stateless([&] {
     S.m = m;
     S.hu.assign(u, u + m);
@@ -459,13 +474,18 @@ static int spline_fit_open_impl(mvus_spline_fit& S, int32_t device, int64_t m, c
     cb.open(device);
     S.du = cb.put(u, (size_t)m);
     S.dX = cb.put(X, 3 * (size_t)m);
+    if (w) {
+      S.dw = cb.put(w, (size_t)m);
+      S.fp_factor = cb.get<double>(1);
+      S.bb = cb.get<dd>(1);
+    }
     S.span = cb.get<int32_t>((size_t)m);
     S.q = cb.get<double>(4 * (size_t)m);
     S.term = cb.get<double>((size_t)m);
     S.tot_part = cb.get<double>(kFitTotalParts);
     S.fp_part = cb.get<double>(512 + kFitSliceBlocks);
     S.fail = cb.get<int>(1);
-    MVUS_HIP(hipStreamSynchronize(cb.st));                 // u and X may go away after this call
+    MVUS_HIP(hipStreamSynchronize(cb.st));                 // u, X and w may go away after this call
     return MVUS_OK;
   });
 }
@@ -487,6 +507,7 @@ static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* 
     CallBuffers& cb = S.cb;
     const double* du = S.du;
     const double* dX = S.dX;
+    const double* dw = S.dw;
     int32_t* span = S.span;
     double* q = S.q;
     double* term = S.term;
@@ -504,6 +525,7 @@ static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* 
     bool precise = false;                                  // double-double from the first ill-conditioned pass on
     bool diag_natural = true;                              // out[0] of the last least-squares pass is the sum FITPACK forms (see fit_band_solve)
     int lsq_dd_n = -1;                                     // knot count whose normal equations w2 holds
+    bool fp_from_factor = false;                           // the last least-squares pass left its f_p in S.fp_factor (k_fit_fp_from_factor)
     MVUS_HIP(hipMemsetAsync(fail, 0, sizeof(int), cb.st));
     std::vector<double> t, fpint, host, b;
     std::vector<int> nrdata;
@@ -530,7 +552,7 @@ static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* 
     nrdata[0] = (int)m - 2;
     auto blocks = fit_blocks;
     auto residual = [&](int ncoef, bool spans, int nspan) {            // c -> f_p (and the per-span residuals), fetched
-      fit_residual_pass(cb.st, (long long)m, ncoef, span, q, dX, cd, term, tot_part, out, spans, nspan, fit_slices(nspan), first, fp_part);
+      fit_residual_pass(cb.st, (long long)m, ncoef, span, q, dX, dw, cd, term, tot_part, out, spans, nspan, fit_slices(nspan), first, fp_part);
       MVUS_HIP(hipGetLastError());
       MVUS_HIP(hipMemcpyAsync(host.data(), out, sizeof(double) * (4 + (spans ? nspan : 0)), hipMemcpyDeviceToHost, cb.st));
       MVUS_HIP(hipMemcpyAsync(&failed, fail, sizeof(int), hipMemcpyDeviceToHost, cb.st));
@@ -542,17 +564,29 @@ static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* 
     auto solve = [&](int ncoef, int nrint_, int n8, bool smoothing, double pinv) {
       for (int attempt = 0; attempt < 2; ++attempt) {
         if (!precise) {
-          if (!smoothing) diag_natural = fit_lsq_pass<double>(cb.st, w1, (long long)m, first, q, dX, ncoef, nrint_, fit_slices(nrint_), band_parts(ncoef, 3, band_parts_min()), cd, out, fail);
+          if (!smoothing) diag_natural = fit_lsq_pass<double>(cb.st, w1, (long long)m, first, q, dX, dw, ncoef, nrint_, fit_slices(nrint_), band_parts(ncoef, 3, band_parts_min()), cd, out, fail);
           else fit_smooth_pass<double>(cb.st, w1, ncoef, n8, bd, pinv, cd, out, fail);
         } else {
           w2.alloc(cb, cap);
           if (lsq_dd_n != n) {
-            diag_natural = fit_lsq_pass<dd>(cb.st, w2, (long long)m, first, q, dX, ncoef, nrint_, fit_slices(nrint_), band_parts(ncoef, 3, band_parts_min()), cd, out, fail);
+            // A weighted fit close to interpolation (the rule at the call of solve below): f_p from the factorisation, for which the
+            // system is solved in ONE chain -- its forward substitution is what k_fit_fp_from_factor reads.  A chain costs 4.8 us a row in
+            // double-double where the partitioned solver takes a fraction of that; at most m / 2 ... m + 2 rows here, and only here: a
+            // weighted pass that is in double-double through the test on the pivots keeps the partition and the residual's own sum.
+            fp_from_factor = dw && 2ll * ncoef > m;
+            diag_natural = fit_lsq_pass<dd>(cb.st, w2, (long long)m, first, q, dX, dw, ncoef, nrint_, fit_slices(nrint_),
+                                            fp_from_factor ? BandParts() : band_parts(ncoef, 3, band_parts_min()), cd, out, fail);
+            if (fp_from_factor && !S.bb_ready) { hipLaunchKernelGGL(k_fit_wx2, dim3(1), dim3(256), 0, cb.st, (long long)m, dX, dw, S.bb); S.bb_ready = true; }
+            if (fp_from_factor) hipLaunchKernelGGL(k_fit_fp_from_factor, dim3(1), dim3(256), 0, cb.st, 3 * ncoef, w2.yw, S.bb, S.fp_factor);
             lsq_dd_n = n;
           }
           if (smoothing) fit_smooth_pass<dd>(cb.st, w2, ncoef, n8, bd, pinv, cd, out, fail);
         }
         residual(ncoef, !smoothing, nrint_);
+        if (precise && fp_from_factor && !smoothing && !failed) {      // f_p of this pass from its factorisation (no floored pivot in it)
+          MVUS_HIP(hipMemcpyAsync(&host[1], S.fp_factor, sizeof(double), hipMemcpyDeviceToHost, cb.st));
+          MVUS_HIP(hipStreamSynchronize(cb.st));
+        }
         ++passes;
         if (std::getenv("MVUS_DEBUG")) std::fprintf(stderr, "spline_smooth: n=%d %s %s  diag(L) %.3e..%.3e  fp %.6e  fail %d\n", n, smoothing ? "smooth" : "lsq",
                                                     precise ? "dd" : "fp64", host[2], host[3], host[1], failed);
@@ -577,6 +611,12 @@ static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* 
       MVUS_HIP(hipStreamSynchronize(cb.st));               // t is modified on the host below
       hipLaunchKernelGGL(k_fit_basis, blocks(m), dim3(256), 0, cb.st, (long long)m, du, td, ncoef, span, q);
       hipLaunchKernelGGL(k_fit_first, blocks(nrint + 1), dim3(256), 0, cb.st, (long long)m, du, td, nrint, first);
+      // A weighted fit goes to double-double once it has more than half as many coefficients as samples.  Close to interpolation a knot
+      // set can be rank deficient to fp64 (cond(A) 5e15 at 313 coefficients for 349 samples in tests/test_gpu_weighted_fit.py, seed 6)
+      // through the growth of the back substitution along a run of one-sample spans, with every Cholesky pivot of ordinary size: the test
+      // on the factor's diagonal below does not see it, the residuals are off by 5 % and the knot search leaves FITPACK's path.  Weights
+      // enter the normal equations squared and use up the margin the unweighted fit has there; that fit keeps its own rule and its bits.
+      if (dw && !precise && 2ll * ncoef > m) precise = true;
       solve(ncoef, nrint, 0, false, 0.0);
       fp = host[1];
       if (ier == -2) fp0 = fp;
@@ -671,15 +711,18 @@ static int spline_fit_run(mvus_spline_fit& S, double s, int32_t* n_out, double* 
   return rc;
 }
 
-int mvus_spline_fit_open(int32_t device, int64_t m, const double* u, const double* X, mvus_spline_fit** out) {
+int mvus_spline_fit_open_w(int32_t device, int64_t m, const double* u, const double* X, const double* w, mvus_spline_fit** out) {
   if (!out) { g_create_error = "spline_fit_open: bad arguments"; return MVUS_E_INVALID; }
   *out = nullptr;
   mvus_spline_fit* S = nullptr;
   try { S = new mvus_spline_fit(); } catch (const std::exception& e) { g_create_error = e.what(); return MVUS_E_INVALID; }
-  const int rc = spline_fit_open_impl(*S, device, m, u, X);
+  const int rc = spline_fit_open_impl(*S, device, m, u, X, w);
   if (rc != MVUS_OK) { delete S; return rc; }
   *out = S;
   return MVUS_OK;
+}
+int mvus_spline_fit_open(int32_t device, int64_t m, const double* u, const double* X, mvus_spline_fit** out) {
+  return mvus_spline_fit_open_w(device, m, u, X, nullptr, out);
 }
 int mvus_spline_fit_smooth(mvus_spline_fit* S, double s, int32_t* n_out, double* t_out, double* c_out, double* fp_out, int32_t* ier_out) {
   if (!S) { g_create_error = "spline_fit_smooth: no session"; return MVUS_E_INVALID; }
@@ -687,13 +730,17 @@ int mvus_spline_fit_smooth(mvus_spline_fit* S, double s, int32_t* n_out, double*
 }
 void mvus_spline_fit_close(mvus_spline_fit* S) { delete S; }
 
-int mvus_spline_smooth(int32_t device, int64_t m, const double* u, const double* X, double s, int32_t* n_out, double* t_out, double* c_out,
-                       double* fp_out, int32_t* ier_out) {
+int mvus_spline_smooth_w(int32_t device, int64_t m, const double* u, const double* X, const double* w, double s, int32_t* n_out, double* t_out,
+                         double* c_out, double* fp_out, int32_t* ier_out) {
   if (!n_out || !t_out || !c_out || !(s > 0.0) || !std::isfinite(s)) { g_create_error = "spline_smooth: bad arguments (m > 3 samples, s > 0)"; return MVUS_E_INVALID; }
   mvus_spline_fit S;
-  const int rc = spline_fit_open_impl(S, device, m, u, X);
+  const int rc = spline_fit_open_impl(S, device, m, u, X, w);
   if (rc != MVUS_OK) return rc;
   return spline_fit_run(S, s, n_out, t_out, c_out, fp_out, ier_out);
+}
+int mvus_spline_smooth(int32_t device, int64_t m, const double* u, const double* X, double s, int32_t* n_out, double* t_out, double* c_out,
+                       double* fp_out, int32_t* ier_out) {
+  return mvus_spline_smooth_w(device, m, u, X, nullptr, s, n_out, t_out, c_out, fp_out, ier_out);
 }
 
 int mvus_spline_band_solve(int32_t device, int32_t n, int32_t hb, int32_t precise, int32_t parts, const double* G5, const double* G5_lo, const double* BtB,
@@ -722,11 +769,11 @@ int mvus_spline_band_diag_sum(int32_t device, int32_t n, int32_t precise, const 
   return stateless([&] { return precise ? band_diag_sum_run<dd>(device, n, G5, G5_lo, out) : band_diag_sum_run<double>(device, n, G5, G5_lo, out); });
 }
 
-int mvus_spline_fit_normal(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, int32_t precise, int32_t slices,
-                           int32_t parts, int32_t* span_out, double* q_out, int64_t* first_out, double* G5_out, double* G5_lo_out, double* rhs_out,
-                           double* rhs_lo_out, double* c_out, double* stats_out, int32_t* fail_out) {
+int mvus_spline_fit_normal_w(int32_t device, int64_t m, const double* u, const double* X, const double* w, int32_t n, const double* t, int32_t precise,
+                             int32_t slices, int32_t parts, int32_t* span_out, double* q_out, int64_t* first_out, double* G5_out, double* G5_lo_out,
+                             double* rhs_out, double* rhs_lo_out, double* c_out, double* stats_out, int32_t* fail_out) {
   if (!X || !span_out || !q_out || !first_out || !G5_out || !rhs_out || !c_out || !stats_out || !fail_out) { g_create_error = "spline_fit_normal: bad arguments"; return MVUS_E_INVALID; }
-  if (!fit_inspect_args_ok("spline_fit_normal", m, u, X, n, t, slices)) return MVUS_E_INVALID;
+  if (!fit_inspect_args_ok("spline_fit_normal", m, u, X, w, n, t, slices)) return MVUS_E_INVALID;
   const int ncoef = n - 4;
   if (parts < -1 || parts == 1 || (parts >= 2 && !band_parts_legal(ncoef, 3, parts))) {
     g_create_error = "spline_fit_normal: parts must be -1 (one chain), 0 (the production rule) or 2..256 interiors of at least 6 rows";
@@ -736,9 +783,15 @@ int mvus_spline_fit_normal(int32_t device, int64_t m, const double* u, const dou
   if (parts == 0) bp = band_parts(ncoef, 3, 192);
   else if (parts >= 2) bp = band_parts_fixed(ncoef, 3, parts);
   return stateless([&] {
-    return precise ? fit_normal_run<dd>(device, m, u, X, n, t, slices, bp, span_out, q_out, first_out, G5_out, G5_lo_out, rhs_out, rhs_lo_out, c_out, stats_out, fail_out)
-                   : fit_normal_run<double>(device, m, u, X, n, t, slices, bp, span_out, q_out, first_out, G5_out, G5_lo_out, rhs_out, rhs_lo_out, c_out, stats_out, fail_out);
+    return precise ? fit_normal_run<dd>(device, m, u, X, w, n, t, slices, bp, span_out, q_out, first_out, G5_out, G5_lo_out, rhs_out, rhs_lo_out, c_out, stats_out, fail_out)
+                   : fit_normal_run<double>(device, m, u, X, w, n, t, slices, bp, span_out, q_out, first_out, G5_out, G5_lo_out, rhs_out, rhs_lo_out, c_out, stats_out, fail_out);
   });
+}
+int mvus_spline_fit_normal(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, int32_t precise, int32_t slices,
+                           int32_t parts, int32_t* span_out, double* q_out, int64_t* first_out, double* G5_out, double* G5_lo_out, double* rhs_out,
+                           double* rhs_lo_out, double* c_out, double* stats_out, int32_t* fail_out) {
+  return mvus_spline_fit_normal_w(device, m, u, X, nullptr, n, t, precise, slices, parts, span_out, q_out, first_out, G5_out, G5_lo_out, rhs_out, rhs_lo_out,
+                                  c_out, stats_out, fail_out);
 }
 
 int mvus_spline_fit_penalty(int32_t device, int32_t ncoef, int32_t n8, const double* b, int32_t precise, double* BtB_out, double* BtB_lo_out) {
@@ -747,23 +800,23 @@ int mvus_spline_fit_penalty(int32_t device, int32_t ncoef, int32_t n8, const dou
   return stateless([&] { return precise ? fit_penalty_run<dd>(device, ncoef, n8, b, BtB_out, BtB_lo_out) : fit_penalty_run<double>(device, ncoef, n8, b, BtB_out, BtB_lo_out); });
 }
 
-int mvus_spline_fit_residual(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, const double* c, int32_t slices,
-                             double* term_out, double* fp_out, double* fpint_out) {
+int mvus_spline_fit_residual_w(int32_t device, int64_t m, const double* u, const double* X, const double* w, int32_t n, const double* t, const double* c,
+                               int32_t slices, double* term_out, double* fp_out, double* fpint_out) {
   if (!X || !c || !term_out || !fp_out || !fpint_out) { g_create_error = "spline_fit_residual: bad arguments"; return MVUS_E_INVALID; }
-  if (!fit_inspect_args_ok("spline_fit_residual", m, u, X, n, t, slices)) return MVUS_E_INVALID;
+  if (!fit_inspect_args_ok("spline_fit_residual", m, u, X, w, n, t, slices)) return MVUS_E_INVALID;
   const int ncoef = n - 4, nspan = n - 7;
   for (int i = 0; i < 3 * ncoef; ++i) if (!std::isfinite(c[i])) { g_create_error = "spline_fit_residual: non-finite coefficient"; return MVUS_E_INVALID; }
   return stateless([&] {
     CallBuffers cb;
     cb.open(device);
     FitInputs in;
-    in.upload(cb, m, u, X, n, t);
+    in.upload(cb, m, u, X, w, n, t);
     const double* cd = cb.put(c, 3 * (size_t)ncoef);
     double* term = cb.get<double>((size_t)m);
     double* tot_part = cb.get<double>(kFitTotalParts);
     double* fp_part = cb.get<double>(512 + kFitSliceBlocks);
     double* out = cb.get<double>((size_t)n + 4);
-    fit_residual_pass(cb.st, (long long)m, ncoef, in.span, in.q, in.dX, cd, term, tot_part, out, true, nspan, slices ? slices : fit_slices(nspan), in.first, fp_part);
+    fit_residual_pass(cb.st, (long long)m, ncoef, in.span, in.q, in.dX, in.dw, cd, term, tot_part, out, true, nspan, slices ? slices : fit_slices(nspan), in.first, fp_part);
     MVUS_HIP(hipGetLastError());
     MVUS_HIP(hipMemcpyAsync(term_out, term, sizeof(double) * m, hipMemcpyDeviceToHost, cb.st));
     MVUS_HIP(hipMemcpyAsync(fp_out, out + 1, sizeof(double), hipMemcpyDeviceToHost, cb.st));
@@ -771,6 +824,10 @@ int mvus_spline_fit_residual(int32_t device, int64_t m, const double* u, const d
     MVUS_HIP(hipStreamSynchronize(cb.st));
     return MVUS_OK;
   });
+}
+int mvus_spline_fit_residual(int32_t device, int64_t m, const double* u, const double* X, int32_t n, const double* t, const double* c, int32_t slices,
+                             double* term_out, double* fp_out, double* fpint_out) {
+  return mvus_spline_fit_residual_w(device, m, u, X, nullptr, n, t, c, slices, term_out, fp_out, fpint_out);
 }
 
 }  // extern "C"

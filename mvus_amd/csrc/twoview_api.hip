@@ -167,6 +167,37 @@ int mvus_triangulate(int32_t device, int64_t N, const double* x1, const double* 
   });
 }
 
+int mvus_triangulate_cov(int32_t device, int64_t N, const double* x1, const double* x2, const double* P1, const double* P2, double sigma1,
+                         double sigma2, double* X, double* cov, double* err1, double* err2) {
+  if (N < 0 || !P1 || !P2 || (N > 0 && (!x1 || !x2 || !X))) { g_create_error = "triangulate_cov: bad arguments"; return MVUS_E_INVALID; }
+  if (!cov) { g_create_error = "triangulate_cov: cov is NULL (mvus_triangulate is the call without a covariance)"; return MVUS_E_INVALID; }
+  if (!std::isfinite(sigma1) || !std::isfinite(sigma2) || !(sigma1 > 0.0) || !(sigma2 > 0.0)) {
+    g_create_error = "triangulate_cov: sigma1 and sigma2 must be finite and > 0";
+    return MVUS_E_INVALID;
+  }
+  if (N == 0) return MVUS_OK;
+  return stateless([&] {
+    CallBuffers cb;
+    cb.open(device);
+    const double* dx1 = cb.put(x1, 2 * (size_t)N);
+    const double* dx2 = cb.put(x2, 2 * (size_t)N);
+    double* dX = cb.get<double>(4 * (size_t)N);
+    double* dC = cb.get<double>(6 * (size_t)N);
+    double* de = cb.get<double>(2 * (size_t)N);
+    TriCams cams;
+    std::memcpy(cams.P1, P1, sizeof(cams.P1)); std::memcpy(cams.P2, P2, sizeof(cams.P2));
+    hipLaunchKernelGGL(k_triangulate_cov, fit_blocks(N), dim3(256), 0, cb.st, cams, sigma1, sigma2, (long long)N, dx1, dx2, dX, dC,
+                       err1 ? de : (double*)nullptr, err2 ? de + N : (double*)nullptr);
+    MVUS_HIP(hipGetLastError());
+    MVUS_HIP(hipMemcpyAsync(X, dX, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipMemcpyAsync(cov, dC, sizeof(double) * 6 * N, hipMemcpyDeviceToHost, cb.st));
+    if (err1) MVUS_HIP(hipMemcpyAsync(err1, de, sizeof(double) * N, hipMemcpyDeviceToHost, cb.st));
+    if (err2) MVUS_HIP(hipMemcpyAsync(err2, de + N, sizeof(double) * N, hipMemcpyDeviceToHost, cb.st));
+    MVUS_HIP(hipStreamSynchronize(cb.st));
+    return MVUS_OK;
+  });
+}
+
 /* cv2.solvePnPRansac(objectPoints, imagePoints, K, d, reprojectionError) as Scene.get_camera_pose calls it (pnp.hip.h) */
 int mvus_pnp_ransac(int32_t device, int64_t N, const double* X, const double* uv, const double* K, const double* d, double reproj_error,
                     int32_t iterations, uint64_t seed, double* rvec, double* tvec, uint8_t* inliers, int64_t* n_inliers) {

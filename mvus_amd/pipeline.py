@@ -199,7 +199,7 @@ def reconstruct_from_config(path, max_iter=10, verbose=False, timer=None, output
     traj_to_spline, the incremental loop, spline_to_traj; with ``settings['ba_position_priors']`` and a position log
     (``path_position_priors``) ``Scene.align_to_position_priors`` and one final LM BA over all cameras that carries the priors; with ``settings['ba_landmarks']`` and the two
     landmark files (``path_landmarks``, ``path_landmark_observations``) ``Scene.align_to_landmarks`` and that final BA with the landmarks (and the priors, when both are configured); ``Scene.ba_covariance`` when ``settings['ba_covariance']`` is true, ``Scene.ba_detection_covariance`` (which then serves both) when ``settings['ba_detection_covariance']`` is; ``Scene.kinematics`` (stage 'kinematics') when
-    ``settings['ba_kinematics']`` is true; ``align_gt`` when the config gives ground truth; the Scene pickled to
+    ``settings['ba_kinematics']`` is true; with ``settings['traj_weights'] = 'triangulation'`` (and ``traj_sigma_px``, ``traj_weight_floor``; read by the Scene's own methods, checked in ``create_scene``) ``init_traj`` / ``triangulate`` / ``traj_to_spline`` carry and use ``Scene.traj_sigma``, which the pickle holds while it is set; ``align_gt`` when the config gives ground truth; the Scene pickled to
     ``settings['path_output']`` when ``output`` and that key is set.  Returns (Scene, StageTimer)."""
     from .reconstruction import common
     timer = timer or StageTimer()

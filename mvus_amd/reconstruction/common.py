@@ -229,12 +229,19 @@ class Scene:
         self.landmarks = None          # (3, L) surveyed static points, or None (settings['ba_landmarks'])
         self.landmark_observations = None      # (6, K): camera id, landmark, u, v, sigma_u, sigma_v
         self.position_priors = None    # (7, K): t, x, y, z, sigma_x, sigma_y, sigma_z of surveyed positions, or None (settings['ba_position_priors'])
+        self.traj_sigma = None         # 1-sigma (sqrt(trace(cov) / 3)) of every column of traj, or None (settings['traj_weights'])
 
     def __getstate__(self):         # the output pickle (main.py:93) carries data only
         state = dict(self.__dict__)
         state['_ba_handle'] = None
         state['_ba_key'] = None
+        if state.get('traj_sigma') is None:      # (carried only when set: without settings['traj_weights'] the pickle has the keys it had)
+            state.pop('traj_sigma', None)
         return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.__dict__.setdefault('traj_sigma', None)
 
     # ---- bookkeeping --------------------------------------------------------------------------
     def addCamera(self, *camera):
@@ -321,9 +328,55 @@ class Scene:
         assert len(smooth_factor) == 2, 'Smoothness should be defined by two parameters (min, max)'
         interval, idx = util.find_intervals(self.traj[0], idx=True)
         device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
-        tck = [_spline.traj_fit(self.traj[:, idx[0, i]:idx[1, i] + 1], smooth_factor, device=device) for i in range(interval.shape[1])]
+        sigma = getattr(self, 'traj_sigma', None)
+        # traj_sigma counts only while it is aligned with traj: code that cuts or reorders self.traj by hand (s.traj = s.traj[:, mask]) and
+        # does not cut traj_sigma with it gets the unweighted fit, said aloud -- sigmas of other samples would be worse than none
+        if sigma is not None and len(sigma) != self.traj.shape[1]:
+            print('traj_to_spline: traj_sigma has %d entries for %d samples -- fitting without weights' % (len(sigma), self.traj.shape[1]))
+        if sigma is not None and len(sigma) == self.traj.shape[1]:
+            # settings['traj_weights']: splprep's w from the 1-sigma of every sample, interval by interval (only the ratios inside a fit matter)
+            floor = self.traj_weights()[2]
+            tck = [_spline.traj_fit(self.traj[:, idx[0, i]:idx[1, i] + 1], smooth_factor, device=device,
+                                    w=self.weights_from_sigma(sigma[idx[0, i]:idx[1, i] + 1], floor)) for i in range(interval.shape[1])]
+        else:
+            tck = [_spline.traj_fit(self.traj[:, idx[0, i]:idx[1, i] + 1], smooth_factor, device=device) for i in range(interval.shape[1])]
         self.spline['tck'], self.spline['int'] = tck, interval
         return self.spline
+
+    def traj_weights(self):
+        """``settings['traj_weights']``: None (absent: every method does what the reference does), or (mode, sigma_px, floor) with mode
+        'triangulation' -- ``init_traj`` and ``triangulate`` then keep the 1-sigma of every triangulated point in ``traj_sigma``
+        (``triangulate_with_cov`` with ``settings['traj_sigma_px']`` pixels of noise: a scalar or one value per camera, default 1) and
+        ``traj_to_spline`` fits with w = max(sigma_min / sigma, ``settings['traj_weight_floor']``) (default 1e-3)."""
+        st = self.settings if isinstance(self.settings, dict) else {}
+        mode = st.get('traj_weights')
+        if mode is None:
+            return None
+        if mode != 'triangulation':
+            raise ValueError("settings['traj_weights'] must be 'triangulation' or absent, not %r" % (mode,))
+        px = np.asarray(st.get('traj_sigma_px', 1.0), dtype=np.float64)
+        if px.ndim > 1 or (px.ndim == 1 and px.size != self.numCam) or not np.all(np.isfinite(px)) or not np.all(px > 0):
+            raise ValueError("settings['traj_sigma_px'] must be a positive number, or one per camera")
+        floor = float(st.get('traj_weight_floor', 1e-3))
+        if not (0.0 < floor <= 1.0):
+            raise ValueError("settings['traj_weight_floor'] must lie in (0, 1]")
+        return mode, np.broadcast_to(px, (self.numCam,)), floor
+
+    @staticmethod
+    def weights_from_sigma(sigma, floor=1e-3):
+        """splprep's w of one trajectory part from the 1-sigma of its samples: max(sigma_min / sigma, floor), the floor where sigma is NaN
+        (a pair without parallax); sigma_min over the finite, positive values of the part."""
+        sigma = np.asarray(sigma, dtype=np.float64)
+        ok = np.isfinite(sigma) & (sigma > 0)
+        w = np.full(sigma.shape, float(floor))
+        if ok.any():
+            w[ok] = np.maximum(sigma[ok].min() / sigma[ok], floor)
+        return w
+
+    @staticmethod
+    def sigma_from_cov(cov):
+        """sqrt(trace(cov) / 3) of (N, 3, 3) covariances: the 1-sigma of an isotropic point with the same total variance (NaN stays NaN)"""
+        return np.sqrt(np.trace(np.asarray(cov, dtype=np.float64), axis1=1, axis2=2) / 3.0)
 
     def spline_to_traj(self, sampling_rate=1, t=None):
         """Discrete 3D points of the splines (common.py:273-301): sampled at a constant rate or at the given timestamps,
@@ -344,6 +397,7 @@ class Scene:
             if m.any():
                 parts.append(np.vstack((ts[m], X[:, m])))
         self.traj = np.hstack(parts)
+        self.traj_sigma = None                                   # samples of the spline: no triangulation behind them
         assert (self.traj[0, 1:] >= self.traj[0, :-1]).all()
         return self.traj
 
@@ -746,6 +800,8 @@ class Scene:
                 c.compose()
         if isinstance(self.traj, np.ndarray) and self.traj.ndim == 2 and self.traj.shape[0] == 4 and self.traj.shape[1]:
             self.traj = np.vstack((self.traj[0], s * (R @ self.traj[1:]) + T[:, None]))
+            if getattr(self, 'traj_sigma', None) is not None:
+                self.traj_sigma = s * np.asarray(self.traj_sigma)
 
     def align_to_position_priors(self):
         """The similarity (Umeyama) that takes the spline at the active priors' times onto their positions, applied to the scene
@@ -1191,23 +1247,42 @@ class Scene:
                 a, b = util.match_overlap(mine, self.detections_global[other])
             except Exception:                       # no temporal overlap with this camera (the reference's bare except)
                 return None
-            Xh, d_new, d_other = ep.triangulate_with_errors(a[1:], b[1:], new_cam.P, self.cameras[other].P, device=device)
+            if weighted is None:
+                Xh, d_new, d_other = ep.triangulate_with_errors(a[1:], b[1:], new_cam.P, self.cameras[other].P, device=device)
+                sig = None
+            else:                                   # the same points and distances, with the 1-sigma of every point
+                Xh, cov, d_new, d_other = ep.triangulate_with_cov(a[1:], b[1:], new_cam.P, self.cameras[other].P, sigma1=weighted[1][cam_id],
+                                                                   sigma2=weighted[1][other], device=device)
+                sig = self.sigma_from_cov(cov)
             pts = np.vstack((a[0], Xh[:3]))
             if thres:
                 ok = (d_new < thres) & (d_other < thres)
                 if verbose:
                     print('{} out of {} points are triangulated'.format(sum(ok), len(d_new)))
                 pts = pts[:, ok]
+                sig = sig if sig is None else sig[ok]
             if verbose:
                 print('{} points are triangulated into the 3D spline'.format(pts.shape[1]))
-            return pts
+            return pts, sig
 
-        found = [pts for pts in map(against, cams) if pts is not None]
-        X_new = np.hstack([np.empty([4, 0])] + found)
+        weighted = self.traj_weights()
+        found = [r for r in map(against, cams) if r is not None]
+        X_new = np.hstack([np.empty([4, 0])] + [pts for pts, _ in found])
         assert not np.any(util.sampling(X_new, covered)[1]), 'Points should not be triangulated into the existing part of the 3D spline'
         self.spline_to_traj(sampling_rate=factor_s2t)
         merged = np.hstack((self.traj, X_new))
-        self.traj = merged[:, np.unique(merged[0], return_index=True)[1]]      # time ordered, one sample per timestamp (the first)
+        if weighted is None:
+            self.traj = merged[:, np.unique(merged[0], return_index=True)[1]]      # time ordered, one sample per timestamp (the first)
+        else:
+            # the samples of the spline come out of a BA: as good as the best raw pair; of several points at one timestamp the one with the
+            # smallest sigma stays (NaN last, then the first) where the reference keeps whichever comes first
+            sig_new = np.concatenate([np.empty(0)] + [sig for _, sig in found])
+            good = sig_new[np.isfinite(sig_new) & (sig_new > 0)]
+            sigma = np.concatenate((np.full(self.traj.shape[1], good.min() if good.size else 1.0), sig_new))
+            key = np.where(np.isfinite(sigma) & (sigma > 0), sigma, np.inf)
+            order = np.lexsort((np.arange(key.size), key, merged[0]))
+            first = order[np.unique(merged[0][order], return_index=True)[1]]
+            self.traj, self.traj_sigma = merged[:, first], sigma[first]
         if refit:
             self.traj_to_spline(smooth_factor=factor_t2s)
         return X_new
@@ -1304,8 +1379,14 @@ class Scene:
         x1, x2 = x1[:, mask], x2[:, mask]
         X, P = ep.triangulate_from_E(E, K1, K2, x1, x2, device=device)
         self.traj = np.vstack((d1[0][keep][mask], X[:-1]))
+        self.traj_sigma = None
         self.cameras[t1].P = K1 @ np.hstack((np.eye(3), np.zeros((3, 1))))
         self.cameras[t2].P = K2 @ P
+        weighted = self.traj_weights()
+        if weighted is not None:                  # the 1-sigma of every point, from the corrected matches and the two P just set
+            _, cov, _, _ = ep.triangulate_with_cov(x1[:2], x2[:2], self.cameras[t1].P, self.cameras[t2].P, sigma1=weighted[1][t1], sigma2=weighted[1][t2],
+                                                   device=device)
+            self.traj_sigma = self.sigma_from_cov(cov)
         self.cameras[t1].decompose()
         self.cameras[t2].decompose()
 
@@ -1490,5 +1571,6 @@ def create_scene(path_input):
         # surveyed static points: id x y z per line, and their clicks: camera id u v [sigma_u sigma_v] per line
         flight.landmarks, flight.landmark_observations = load_landmarks(opt['path_landmarks'], opt['path_landmark_observations'], opt.get('landmark_sigma'))
     flight.ba_landmarks()                    # (settings['ba_landmarks'] likewise)
+    flight.traj_weights()                    # (settings['traj_weights'], ['traj_sigma_px'], ['traj_weight_floor'] likewise)
     print('Input data are loaded successfully, a scene is created.\n')
     return flight

@@ -2,7 +2,8 @@
 
 * ``triangulate_matlab`` (epipolar.py:497-510), called per camera pair by ``Scene.triangulate`` (common.py:783) -- there a
   Python loop with one 4x4 ``np.linalg.svd`` per point, here one lane per point in ``k_triangulate``
-  (csrc/triangulate.hip.h, one-sided Jacobi SVD) through ``mvus_triangulate``;
+  (csrc/triangulate.hip.h, one-sided Jacobi SVD) through ``mvus_triangulate``; ``triangulate_with_cov`` adds the covariance of
+  every point (``k_triangulate_cov`` through ``mvus_triangulate_cov``; no reference counterpart);
 * ``computeFundamentalMat`` (epipolar.py:92-118, ``cv2.findFundamentalMat(FM_RANSAC)``) and its batched form
   ``fundamental_ransac_batch`` (one call for many independent point sets: ``synchronization.sync_bf``), through
   ``mvus_fundamental_ransac``;
@@ -50,6 +51,30 @@ def triangulate_with_errors(x1, x2, P1, P2, device=0):
     """triangulate_matlab plus the reprojection distances in both cameras (what Scene.triangulate thresholds,
     common.py:786-789), computed in the same kernel."""
     return _call(x1, x2, P1, P2, True, device)
+
+
+def triangulate_with_cov(x1, x2, P1, P2, sigma1=1.0, sigma2=1.0, device=0):
+    """triangulate_with_errors plus the covariance of every point (``mvus_triangulate_cov``, the same kernel work and the same bits of
+    X, d1, d2): returns (Xh 4 x N, cov N x 3 x 3, d1, d2).  ``cov`` is the Gauss-Newton covariance (A^T A)^-1 of the point at Xh for
+    isotropic pixel noise ``sigma1`` / ``sigma2`` (1-sigma, px) in the two cameras, symmetric to the bit; NaN for a pair without
+    parallax, with a non-finite point or a point behind a camera.  No reference counterpart."""
+    lib = _lib.load()
+    x1 = np.ascontiguousarray(np.asarray(x1, dtype=np.float64)[:2])
+    x2 = np.ascontiguousarray(np.asarray(x2, dtype=np.float64)[:2])
+    if x1.shape != x2.shape or x1.ndim != 2:
+        raise ValueError('x1 and x2 must both be (2 or 3) x N')
+    P1 = np.ascontiguousarray(P1, dtype=np.float64)
+    P2 = np.ascontiguousarray(P2, dtype=np.float64)
+    if P1.shape != (3, 4) or P2.shape != (3, 4):
+        raise ValueError('P1 and P2 must be 3 x 4')
+    N = x1.shape[1]
+    X, c6, e1, e2 = np.empty((4, N)), np.empty((6, N)), np.empty(N), np.empty(N)
+    rc = lib.mvus_triangulate_cov(int(device), N, _lib.dptr(x1), _lib.dptr(x2), _lib.dptr(P1), _lib.dptr(P2), float(sigma1), float(sigma2),
+                                  _lib.dptr(X), _lib.dptr(c6), _lib.dptr(e1), _lib.dptr(e2))
+    if rc != 0:
+        raise (ValueError if rc == _lib.MVUS_E_INVALID else RuntimeError)('mvus_triangulate_cov: ' + lib.mvus_last_error(None).decode())
+    cov = c6[[0, 1, 2, 1, 3, 4, 2, 4, 5]].T.reshape(N, 3, 3)      # xx xy xz / xy yy yz / xz yz zz: both halves from the same six values
+    return X, np.ascontiguousarray(cov), e1, e2
 
 
 def reprojection_error(x, x_p):

@@ -146,9 +146,19 @@ def lsq_fit(knots, t, X, device=0):
     return [c[0].copy(), c[1].copy(), c[2].copy()]
 
 
-def smooth_fit(t, X, s, device=0, full_output=False):
-    """``scipy.interpolate.splprep(X, u=t, s=s, k=3)[0]``: the tck ``[knots, [cx, cy, cz], 3]`` of the smoothing cubic spline
-    through X[3, m] at the strictly increasing timestamps t[m].  ``full_output``: also (fp, ier) as FITPACK reports them."""
+def _weights(w, m):
+    """splprep's ``w`` as the library takes it: a contiguous float64[m] (its values are checked there: finite and > 0)"""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (m,):
+        raise ValueError('w has shape %s, expected (%d,): one weight per sample' % (w.shape, m))
+    return w
+
+
+def smooth_fit(t, X, s, device=0, full_output=False, w=None):
+    """``scipy.interpolate.splprep(X, w=w, u=t, s=s, k=3)[0]``: the tck ``[knots, [cx, cy, cz], 3]`` of the smoothing cubic spline
+    through X[3, m] at the strictly increasing timestamps t[m].  ``full_output``: also (fp, ier) as FITPACK reports them.
+    ``w``: None (unit weights, the reference's call), or one finite positive weight per sample, 1 / sigma of the sample up to a common
+    factor (``mvus_spline_smooth_w``); ``fp`` is then the weighted residual sum that ``s`` is compared with."""
     lib = _lib.load()
     t = np.ascontiguousarray(t, dtype=np.float64)
     X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
@@ -160,10 +170,15 @@ def smooth_fit(t, X, s, device=0, full_output=False):
     fp = ctypes.c_double(0.0)
     knots = np.zeros(nest)
     c = np.zeros((3, nest))
-    rc = lib.mvus_spline_smooth(int(device), t.size, _lib.dptr(t), _lib.dptr(X), float(s), ctypes.byref(n), _lib.dptr(knots), _lib.dptr(c),
-                                ctypes.byref(fp), ctypes.byref(ier))
+    if w is None:
+        rc = lib.mvus_spline_smooth(int(device), t.size, _lib.dptr(t), _lib.dptr(X), float(s), ctypes.byref(n), _lib.dptr(knots), _lib.dptr(c),
+                                    ctypes.byref(fp), ctypes.byref(ier))
+    else:
+        w = _weights(w, t.size)
+        rc = lib.mvus_spline_smooth_w(int(device), t.size, _lib.dptr(t), _lib.dptr(X), _lib.dptr(w), float(s), ctypes.byref(n), _lib.dptr(knots),
+                                      _lib.dptr(c), ctypes.byref(fp), ctypes.byref(ier))
     if rc != 0:
-        _err(lib, rc, 'mvus_spline_smooth')
+        _err(lib, rc, 'mvus_spline_smooth' if w is None else 'mvus_spline_smooth_w')
     nk = n.value
     tck = [knots[:nk].copy(), [c[d, :nk - 4].copy() for d in range(3)], 3]
     return (tck, fp.value, ier.value) if full_output else tck
@@ -171,13 +186,14 @@ def smooth_fit(t, X, s, device=0, full_output=False):
 
 class SmoothFit:
     """``smooth_fit`` for several smoothing factors on ONE set of samples: the samples are checked and uploaded once and the
-    device work arrays are kept (``mvus_spline_fit_open`` / ``_smooth`` / ``_close``) -- what ``traj_fit``'s loop needs.
+    device work arrays are kept (``mvus_spline_fit_open`` / ``_smooth`` / ``_close``) -- what ``traj_fit``'s loop needs.  ``w`` as in
+    ``smooth_fit`` (``mvus_spline_fit_open_w``): the weights belong to the session.
 
         with SmoothFit(t, X) as fit:
             tck = fit(s)
     """
 
-    def __init__(self, t, X, device=0):
+    def __init__(self, t, X, device=0, w=None):
         self.lib = _lib.load()
         t = np.ascontiguousarray(t, dtype=np.float64)
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
@@ -185,10 +201,14 @@ class SmoothFit:
             raise ValueError('X must be 3 x len(t)')
         self.m = t.size
         self.h = ctypes.c_void_p()
-        rc = self.lib.mvus_spline_fit_open(int(device), t.size, _lib.dptr(t), _lib.dptr(X), ctypes.byref(self.h))
+        if w is None:
+            rc = self.lib.mvus_spline_fit_open(int(device), t.size, _lib.dptr(t), _lib.dptr(X), ctypes.byref(self.h))
+        else:
+            w = _weights(w, t.size)
+            rc = self.lib.mvus_spline_fit_open_w(int(device), t.size, _lib.dptr(t), _lib.dptr(X), _lib.dptr(w), ctypes.byref(self.h))
         if rc != 0:
             self.h = None
-            _err(self.lib, rc, 'mvus_spline_fit_open')
+            _err(self.lib, rc, 'mvus_spline_fit_open' if w is None else 'mvus_spline_fit_open_w')
         nest = self.m + 6
         self._knots = np.zeros(nest)
         self._c = np.zeros((3, nest))
@@ -287,11 +307,12 @@ def _fit_samples(u, X, t):
     return u, X, t
 
 
-def fit_normal(u, X, t, precise=False, slices=0, parts=0, device=0):
+def fit_normal(u, X, t, precise=False, slices=0, parts=0, device=0, w=None):
     """One least-squares pass of the smoothing fit on the knots ``t`` (``mvus_spline_fit_normal``, an inspection hook): k_fit_basis,
     k_fit_first, then the fit's own assembly and banded solve, in fp64 or (``precise``) double-double.  ``slices`` = 0: the fit's
     rule, >= 1: that many slices per span; ``parts`` as in ``band_solve``.  Returns a namespace: span[m], q[m, 4], first[nspan + 1],
-    G5 / G5_lo[ncoef, 5], rhs / rhs_lo[3, ncoef], c[3, ncoef], stats[4], fail."""
+    G5 / G5_lo[ncoef, 5], rhs / rhs_lo[3, ncoef], c[3, ncoef], stats[4], fail.  ``w``: the pass of a weighted fit
+    (``mvus_spline_fit_normal_w``): the normal equations of the rows w_i h, right-hand sides w_i X_i; q stays the unweighted basis."""
     from types import SimpleNamespace
     lib = _lib.load()
     u, X, t = _fit_samples(u, X, t)
@@ -300,11 +321,15 @@ def fit_normal(u, X, t, precise=False, slices=0, parts=0, device=0):
     span, q, first = np.zeros(m, np.int32), np.zeros((m, 4)), np.zeros(ns + 1, np.int64)
     G5, G5_lo, rhs, rhs_lo, c, stats = np.zeros((nc, 5)), np.zeros((nc, 5)), np.zeros((3, nc)), np.zeros((3, nc)), np.zeros((3, nc)), np.zeros(4)
     fail = ctypes.c_int32(0)
-    rc = lib.mvus_spline_fit_normal(int(device), m, _lib.dptr(u), _lib.dptr(X), n, _lib.dptr(t), int(bool(precise)), int(slices), int(parts),
-                                    span.ctypes.data_as(_lib.c_int32_p), _lib.dptr(q), first.ctypes.data_as(_lib.c_int64_p), _lib.dptr(G5), _lib.dptr(G5_lo),
-                                    _lib.dptr(rhs), _lib.dptr(rhs_lo), _lib.dptr(c), _lib.dptr(stats), ctypes.byref(fail))
+    tail = (n, _lib.dptr(t), int(bool(precise)), int(slices), int(parts), span.ctypes.data_as(_lib.c_int32_p), _lib.dptr(q), first.ctypes.data_as(_lib.c_int64_p),
+            _lib.dptr(G5), _lib.dptr(G5_lo), _lib.dptr(rhs), _lib.dptr(rhs_lo), _lib.dptr(c), _lib.dptr(stats), ctypes.byref(fail))
+    if w is None:
+        rc = lib.mvus_spline_fit_normal(int(device), m, _lib.dptr(u), _lib.dptr(X), *tail)
+    else:
+        w = _weights(w, m)
+        rc = lib.mvus_spline_fit_normal_w(int(device), m, _lib.dptr(u), _lib.dptr(X), _lib.dptr(w), *tail)
     if rc != 0:
-        _err(lib, rc, 'mvus_spline_fit_normal')
+        _err(lib, rc, 'mvus_spline_fit_normal' if w is None else 'mvus_spline_fit_normal_w')
     return SimpleNamespace(span=span, q=q, first=first, G5=G5, G5_lo=G5_lo, rhs=rhs, rhs_lo=rhs_lo, c=c, stats=stats, fail=fail.value)
 
 
@@ -323,10 +348,11 @@ def fit_penalty(b, ncoef, precise=False, device=0):
     return BtB, BtB_lo
 
 
-def fit_residual(u, X, t, c, slices=0, device=0):
+def fit_residual(u, X, t, c, slices=0, device=0, w=None):
     """The residual pass of the smoothing fit for coefficients ``c[3, ncoef]`` on the knots ``t`` (``mvus_spline_fit_residual``, an
     inspection hook): returns a namespace with term[m] (squared residual per sample), fp (their total) and fpint[nspan] (per span,
-    the sample that opens a span shared half / half with the span before)."""
+    the sample that opens a span shared half / half with the span before).  ``w``: the pass of a weighted fit
+    (``mvus_spline_fit_residual_w``): term[i] = |w_i (s(u_i) - X_i)|^2."""
     from types import SimpleNamespace
     lib = _lib.load()
     u, X, t = _fit_samples(u, X, t)
@@ -335,10 +361,14 @@ def fit_residual(u, X, t, c, slices=0, device=0):
     if c.shape != (3, n - 4):
         raise ValueError('c has shape %s, expected (3, %d)' % (c.shape, n - 4))
     term, fp, fpint = np.zeros(m), np.zeros(1), np.zeros(max(n - 7, 1))
-    rc = lib.mvus_spline_fit_residual(int(device), m, _lib.dptr(u), _lib.dptr(X), n, _lib.dptr(t), _lib.dptr(c), int(slices), _lib.dptr(term), _lib.dptr(fp),
-                                      _lib.dptr(fpint))
+    tail = (n, _lib.dptr(t), _lib.dptr(c), int(slices), _lib.dptr(term), _lib.dptr(fp), _lib.dptr(fpint))
+    if w is None:
+        rc = lib.mvus_spline_fit_residual(int(device), m, _lib.dptr(u), _lib.dptr(X), *tail)
+    else:
+        w = _weights(w, m)
+        rc = lib.mvus_spline_fit_residual_w(int(device), m, _lib.dptr(u), _lib.dptr(X), _lib.dptr(w), *tail)
     if rc != 0:
-        _err(lib, rc, 'mvus_spline_fit_residual')
+        _err(lib, rc, 'mvus_spline_fit_residual' if w is None else 'mvus_spline_fit_residual_w')
     return SimpleNamespace(term=term, fp=float(fp[0]), fpint=fpint)
 
 
@@ -370,7 +400,9 @@ def linear_fit_as_cubic(part, s):
     The kernels of this library evaluate CUBIC splines only, so the piecewise-linear curve is returned degree-elevated: the
     same curve, point for point, as a cubic tck (knots [a x4, b x4], or [a x4, u2 x3, b x4] for the bent one).  Documented
     divergence: ``tck[2]`` is 3 where the reference stores 1, and the knot / coefficient arrays differ accordingly; every
-    evaluation (spline_to_traj, the BA residual) gives the reference's values."""
+    evaluation (spline_to_traj, the BA residual) gives the reference's values.
+
+    Unweighted: a weighted ``traj_fit`` fits such a part at unit weights too (three samples, a host restatement of the k = 1 case)."""
     part = np.asarray(part, dtype=np.float64)
     m = part.shape[1]
     u, X = part[0], part[1:]
@@ -437,10 +469,12 @@ def linear_fit_as_cubic(part, s):
     return [np.array(knots, dtype=np.float64), [C[0].copy(), C[1].copy(), C[2].copy()], 3]
 
 
-def traj_fit(part, smooth_factor, device=0):
+def traj_fit(part, smooth_factor, device=0, w=None):
     """One interval of ``Scene.traj_to_spline`` (reference common.py:236-262): ``part`` = [t; x; y; z] (4, m).  The smoothing
     factor starts at 1e-6 * duration and is divided by 1.5 / doubled until duration / #coefficients lies between the two
-    ``smooth_factor`` bounds (or the fit is down to 4 coefficients and still too dense).  Returns the tck."""
+    ``smooth_factor`` bounds (or the fit is down to 4 coefficients and still too dense).  Returns the tck.  ``w``: one weight per
+    sample as in ``smooth_fit``; only their ratios matter here, since the loop rescales s until the knot density fits.  A part of
+    fewer than four samples is fitted without them (``linear_fit_as_cubic``)."""
     lo, hi = min(smooth_factor), max(smooth_factor)
     part = np.ascontiguousarray(part, dtype=np.float64)     # once, not in each of the dozen fits below (a column slice of the trajectory is strided)
     measure = part[0, -1] - part[0, 0]
@@ -448,7 +482,7 @@ def traj_fit(part, smooth_factor, device=0):
     if part.shape[1] < 4:                        # splprep(k=3) raises -> the reference's k=1 fallback (common.py:266-267)
         return linear_fit_as_cubic(part, s)
     prev, direction = 0, 0
-    with SmoothFit(part[0], part[1:], device=device) as fit:       # one upload for the dozen fits of the loop
+    with SmoothFit(part[0], part[1:], device=device, w=w) as fit:       # one upload for the dozen fits of the loop
         while True:
             tck = fit(s)
             n = len(tck[0]) - 4
