@@ -716,6 +716,36 @@ int mvus_correct_matches(int32_t device, int64_t N, const double* F, const doubl
  * MVUS_E_NUMERIC: no candidate puts any point in front of a camera.  Stateless; no CPU fallback. */
 int mvus_pose_from_essential(int32_t device, int64_t N, const double* E, const double* x1n, const double* x2n, double* P2_out, double* X_out);
 
+/* The iterative time-shift search of Albl et al. as the reference runs it (synchronization.py:13-130, "sync_method": "iter") for one
+ * camera pair (sync_iter.hip.h; synchronization.sync_iter_gpu drives it).  The session is opaque.  open uploads, once: both cameras'
+ * interpolating cubic splines in FITPACK form (n coefficients per coordinate, knots[n + 4], coef = x[n] then y[n]; camera 1 on its
+ * timeline t / alpha, camera 2 on its OWN unshifted timeline), camera 2's contiguous intervals as K [start, end) pairs
+ * (util.find_intervals), camera 1's detections detect1[3 * N1] (t(N1) x(N1) y(N1), t ascending) and camera 2's timestamps t2[N2].
+ * `shift` below is the current estimate of beta: camera 2's samples lie at t2 + shift on camera 1's timeline.
+ *
+ * round: both signs of d in one sequence of launches with one synchronisation.  Per sign H hypotheses of nine samples drawn below
+ * min(N1, N2) - 2 |d| by a counter-based sampler (seed, round, sign, hypothesis): the finite real eigenvalues beta of the pencil
+ * A1 + beta A2 (up to six), per beta the normalised 8-point fundamental matrix of (s1, s2 + beta ds) and the model (F, beta d),
+ * scored over all of camera 1's detections: tau = t1 - shift + beta d, overlap when start <= tau < end for an interval, inlier when
+ * the squared Sampson error (epipolar.py:258-265, pixels) of (detection, S2(tau)) is < threshold.  ratio = inliers / overlap; the
+ * highest wins with strict >, in (hypothesis, slot) order, from 0; overlap 0 is skipped.  out[8]: for +d then -d the winner's
+ * -beta d (the reference's -result[-1]), its ratio, inliers, overlap (zeros without a winner).
+ * models (an inspection hook, like mvus_ba_lm_step): one sign -- d carries it -- with explicit sample indices idx[9 * H] into t2;
+ * betas[6 * H] ascending per hypothesis, valid[6 * H], F[9 * 6 * H] (row-major, unit norm, F[2][2] >= 0, x2^T F x1 = 0; zeros for
+ * an empty slot) and counts[2 * 6 * H] (inliers, overlap per model).  A hypothesis with a repeated timestamp, a non-finite sample
+ * or a degenerate one has no valid slot.
+ * score: counts[2 * M] of M models handed in, models[11 * M] = F (9), beta d, valid flag; a model that is not finite counts 0, 0.
+ * MVUS_E_INVALID: bad arguments, fewer than nine samples to draw from (nothing is launched), an index outside t2.  No CPU
+ * fallback. */
+typedef struct mvus_sync_iter mvus_sync_iter;
+int mvus_sync_iter_open(int32_t device, int32_t n1, const double* knots1, const double* coef1, int32_t n2, const double* knots2, const double* coef2,
+                        int32_t K, const double* intervals2, int64_t N1, const double* detect1, int64_t N2, const double* t2, mvus_sync_iter** out);
+void mvus_sync_iter_close(mvus_sync_iter* session);
+int mvus_sync_iter_round(mvus_sync_iter* session, double shift, int32_t d, int32_t H, double threshold, uint64_t seed, int32_t round, double* out);
+int mvus_sync_iter_models(mvus_sync_iter* session, double shift, int32_t d, int32_t H, const int64_t* idx, double threshold, double* betas,
+                          uint8_t* valid, double* F, int32_t* counts);
+int mvus_sync_iter_score(mvus_sync_iter* session, double shift, int64_t M, const double* models, double threshold, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

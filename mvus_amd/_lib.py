@@ -153,6 +153,14 @@ API = [
                                                ctypes.c_uint64, c_double_p, c_uint8_p, c_int32_p]),
     ('mvus_correct_matches', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ('mvus_pose_from_essential', ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ('mvus_sync_iter_open', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_int32,
+                                           c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int64, c_double_p, ctypes.POINTER(ctypes.c_void_p)]),
+    ('mvus_sync_iter_close', None, [ctypes.c_void_p]),
+    ('mvus_sync_iter_round', ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_uint64, ctypes.c_int32,
+                                            c_double_p]),
+    ('mvus_sync_iter_models', ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, c_int64_p, ctypes.c_double, c_double_p, c_uint8_p,
+                                             c_double_p, c_int32_p]),
+    ('mvus_sync_iter_score', ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_int64, c_double_p, ctypes.c_double, c_int32_p]),
 ]
 
 _lib = None

@@ -11,8 +11,47 @@
 #include "triangulate.hip.h"
 #include "pnp.hip.h"
 #include "epipolar.hip.h"
+#include "sync_iter.hip.h"
 
 using namespace mvus;
+
+// ---- iterative time-shift search (sync_iter.hip.h): the session ---------------------------------------------------------------
+// `mem` holds what open uploads, `work` the per-round buffers, which grow with the number of models asked for.
+struct mvus_sync_iter {
+  int device = 0;
+  hipStream_t st = nullptr;
+  DeviceOwner mem, work;
+  SiView v{};
+  long long cap_h = 0, cap_m = 0;                // hypotheses (both signs) and models the work buffers hold
+  double *samp = nullptr, *betas = nullptr, *models = nullptr, *out = nullptr;
+  uint8_t* valid = nullptr;
+  int32_t* counts = nullptr;
+  long long* idx = nullptr;
+  template <class T>
+  const T* put(const T* host, size_t count) {
+    T* d = mem.device<T>(count);
+    if (count) MVUS_HIP(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return d;
+  }
+  void reserve(long long hyps, long long nmodels) {
+    if (hyps <= cap_h && nmodels <= cap_m) return;
+    MVUS_HIP(hipStreamSynchronize(st));
+    work.reset();
+    cap_h = std::max(hyps, cap_h); cap_m = std::max(nmodels, cap_m);
+    samp = work.device<double>((size_t)cap_h * kSiSampDoubles);
+    betas = work.device<double>((size_t)cap_h * kSiSlots);
+    valid = work.device<uint8_t>((size_t)cap_h * kSiSlots);
+    idx = work.device<long long>((size_t)cap_h * kSiSample);
+    models = work.device<double>((size_t)cap_m * kSiModel);
+    counts = work.device<int32_t>((size_t)cap_m * 2);
+    out = work.device<double>(8);
+  }
+  ~mvus_sync_iter() {
+    if (st) { (void)hipStreamSynchronize(st); }
+    work.reset(); mem.reset();
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
 
 // ---- two-view geometry (epipolar.hip.h): host halves ------------------------------------------------------------------------
 namespace {
@@ -459,6 +498,130 @@ int mvus_pose_from_essential(int32_t device, int64_t N, const double* E, const d
     MVUS_HIP(hipMemcpyAsync(X_out, dX, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, cb.st));
     MVUS_HIP(hipStreamSynchronize(cb.st));
     std::memcpy(P2_out, cand.P2[chosen], sizeof(double) * 12);
+    return MVUS_OK;
+  });
+}
+
+// ---- iterative time-shift search (sync_iter.hip.h) ---------------------------------------------------------------------------
+namespace {
+bool si_all_finite(const double* x, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; }
+bool si_knots_ok(int n, const double* t) {
+  if (n < 4 || !si_all_finite(t, (size_t)n + 4)) return false;
+  for (int i = 0; i + 1 < n + 4; ++i) if (t[i] > t[i + 1]) return false;
+  return t[3] < t[n];
+}
+// the score of the session's first `count` models: counts zeroed, one workgroup per (model, tile)
+void si_launch_score(mvus_sync_iter* S, double shift, long long count, double threshold) {
+  MVUS_HIP(hipMemsetAsync(S->counts, 0, sizeof(int32_t) * 2 * count, S->st));
+  const unsigned tiles = (unsigned)((S->v.N1 + kSiScoreTile - 1) / kSiScoreTile);
+  hipLaunchKernelGGL(k_si_score, dim3((unsigned)count, tiles), dim3(256), 0, S->st, S->v, shift, S->models, threshold, S->counts);
+}
+constexpr int kSiMaxHyp = 1 << 20;
+}  // namespace
+
+int mvus_sync_iter_open(int32_t device, int32_t n1, const double* knots1, const double* coef1, int32_t n2, const double* knots2, const double* coef2,
+                        int32_t K, const double* intervals2, int64_t N1, const double* detect1, int64_t N2, const double* t2, mvus_sync_iter** out) {
+  if (!out) return epi_fail("sync_iter_open: bad arguments", MVUS_E_INVALID);
+  *out = nullptr;
+  if (!knots1 || !coef1 || !knots2 || !coef2 || K < 0 || (K > 0 && !intervals2) || N1 < 1 || N2 < 1 || N1 > (1ll << 30) || N2 > (1ll << 30) || !detect1 || !t2)
+    return epi_fail("sync_iter_open: bad arguments (two splines, K >= 0 intervals, at least one sample per camera)", MVUS_E_INVALID);
+  if (!si_knots_ok(n1, knots1) || !si_knots_ok(n2, knots2))
+    return epi_fail("sync_iter_open: a spline needs at least 4 coefficients and finite ascending knots", MVUS_E_INVALID);
+  if (!si_all_finite(coef1, 2 * (size_t)n1) || !si_all_finite(coef2, 2 * (size_t)n2)) return epi_fail("sync_iter_open: non-finite spline coefficient", MVUS_E_INVALID);
+  mvus_sync_iter* S = nullptr;
+  try { S = new mvus_sync_iter(); } catch (const std::exception& e) { g_create_error = e.what(); return MVUS_E_INVALID; }
+  const int rc = stateless([&] {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device || device < 0) throw HipError{"no usable HIP device (libmvusba has no CPU fallback)"};
+    S->device = device;
+    MVUS_HIP(hipSetDevice(device));
+    MVUS_HIP(hipStreamCreateWithFlags(&S->st, hipStreamNonBlocking));
+    SiView& v = S->v;
+    v.n1 = n1; v.n2 = n2; v.K = K; v.N1 = N1; v.N2 = N2;
+    v.t1k = S->put(knots1, (size_t)n1 + 4); v.c1 = S->put(coef1, 2 * (size_t)n1);
+    v.t2k = S->put(knots2, (size_t)n2 + 4); v.c2 = S->put(coef2, 2 * (size_t)n2);
+    v.iv = S->put(intervals2, 2 * (size_t)K);
+    v.d1 = S->put(detect1, 3 * (size_t)N1);
+    v.t2 = S->put(t2, (size_t)N2);
+    MVUS_HIP(hipStreamSynchronize(S->st));
+    return MVUS_OK;
+  });
+  if (rc != MVUS_OK) { delete S; return rc; }
+  *out = S;
+  return MVUS_OK;
+}
+
+void mvus_sync_iter_close(mvus_sync_iter* S) { delete S; }
+
+int mvus_sync_iter_round(mvus_sync_iter* S, double shift, int32_t d, int32_t H, double threshold, uint64_t seed, int32_t round, double* out) {
+  if (!S || !out || H < 1 || H > kSiMaxHyp || d == 0 || d == INT32_MIN || !std::isfinite(shift) || !(threshold > 0.0) || round < 0)
+    return epi_fail("sync_iter_round: bad arguments (a session, H >= 1, d != 0, finite shift, threshold > 0)", MVUS_E_INVALID);
+  const long long n = std::min(S->v.N1, S->v.N2) - 2ll * std::llabs((long long)d);
+  if (n < kSiSample) return epi_fail("sync_iter_round: fewer than nine samples to draw from (min(N1, N2) - 2 |d| < 9)", MVUS_E_INVALID);
+  return stateless([&] {
+    MVUS_HIP(hipSetDevice(S->device));
+    const long long Mper = (long long)H * kSiSlots;
+    S->reserve(2ll * H, 2 * Mper);
+    hipLaunchKernelGGL(k_si_hypotheses, dim3((H + 63) / 64, 2), dim3(64), 0, S->st, S->v, shift, (int)d, (int)H, (unsigned long long)seed, (int)round, n,
+                       (const long long*)nullptr, S->samp, S->betas, S->valid);
+    hipLaunchKernelGGL(k_si_models, dim3((unsigned)((2 * Mper + 63) / 64)), dim3(64), 0, S->st, (int)d, (int)H, 2, S->samp, S->betas, S->valid, S->models);
+    si_launch_score(S, shift, 2 * Mper, threshold);
+    hipLaunchKernelGGL(k_si_select, dim3(2), dim3(256), 0, S->st, Mper, S->models, S->counts, S->out);
+    MVUS_HIP(hipGetLastError());
+    MVUS_HIP(hipMemcpyAsync(out, S->out, sizeof(double) * 8, hipMemcpyDeviceToHost, S->st));
+    MVUS_HIP(hipStreamSynchronize(S->st));
+    return MVUS_OK;
+  });
+}
+
+int mvus_sync_iter_models(mvus_sync_iter* S, double shift, int32_t d, int32_t H, const int64_t* idx, double threshold, double* betas, uint8_t* valid,
+                          double* F, int32_t* counts) {
+  if (!S || !idx || !betas || !valid || !F || !counts || H < 1 || H > kSiMaxHyp || d == 0 || d == INT32_MIN || !std::isfinite(shift) || !(threshold > 0.0))
+    return epi_fail("sync_iter_models: bad arguments (a session, H >= 1, d != 0, finite shift, threshold > 0)", MVUS_E_INVALID);
+  for (int64_t i = 0; i < (int64_t)H * kSiSample; ++i)
+    if (idx[i] < 0 || idx[i] >= S->v.N2) return epi_fail("sync_iter_models: sample index outside camera 2's detections", MVUS_E_INVALID);
+  return stateless([&] {
+    MVUS_HIP(hipSetDevice(S->device));
+    const long long Mper = (long long)H * kSiSlots;
+    S->reserve(H, Mper);
+    static_assert(sizeof(long long) == sizeof(int64_t), "index width");
+    MVUS_HIP(hipMemcpyAsync(S->idx, idx, sizeof(int64_t) * H * kSiSample, hipMemcpyHostToDevice, S->st));
+    // (d carries its own sign here: one sign, the hypotheses of blockIdx.y = 0)
+    hipLaunchKernelGGL(k_si_hypotheses, dim3((H + 63) / 64, 1), dim3(64), 0, S->st, S->v, shift, (int)d, (int)H, 0ull, 0, (long long)S->v.N2,
+                       (const long long*)S->idx, S->samp, S->betas, S->valid);
+    hipLaunchKernelGGL(k_si_models, dim3((unsigned)((Mper + 63) / 64)), dim3(64), 0, S->st, (int)d, (int)H, 1, S->samp, S->betas, S->valid, S->models);
+    si_launch_score(S, shift, Mper, threshold);
+    MVUS_HIP(hipGetLastError());
+    std::vector<double> hm((size_t)Mper * kSiModel);
+    MVUS_HIP(hipMemcpyAsync(hm.data(), S->models, sizeof(double) * hm.size(), hipMemcpyDeviceToHost, S->st));
+    MVUS_HIP(hipMemcpyAsync(betas, S->betas, sizeof(double) * Mper, hipMemcpyDeviceToHost, S->st));
+    MVUS_HIP(hipMemcpyAsync(valid, S->valid, (size_t)Mper, hipMemcpyDeviceToHost, S->st));
+    MVUS_HIP(hipMemcpyAsync(counts, S->counts, sizeof(int32_t) * 2 * Mper, hipMemcpyDeviceToHost, S->st));
+    MVUS_HIP(hipStreamSynchronize(S->st));
+    for (long long m = 0; m < Mper; ++m) std::memcpy(F + 9 * m, hm.data() + kSiModel * m, sizeof(double) * 9);
+    return MVUS_OK;
+  });
+}
+
+int mvus_sync_iter_score(mvus_sync_iter* S, double shift, int64_t M, const double* models, double threshold, int32_t* counts) {
+  if (!S || M < 0 || M > (1ll << 24) || (M > 0 && (!models || !counts)) || !std::isfinite(shift) || !(threshold > 0.0))
+    return epi_fail("sync_iter_score: bad arguments (a session, 0 <= M <= 2^24 models, finite shift, threshold > 0)", MVUS_E_INVALID);
+  if (M == 0) return MVUS_OK;
+  return stateless([&] {
+    MVUS_HIP(hipSetDevice(S->device));
+    S->reserve(0, M);
+    // a model handed in is scored when its flag is set and its eleven numbers are finite
+    std::vector<double> hm(models, models + (size_t)M * kSiModel);
+    for (int64_t m = 0; m < M; ++m) {
+      bool ok = hm[kSiModel * m + 10] != 0.0;
+      for (int a = 0; a < kSiModel; ++a) ok = ok && std::isfinite(hm[kSiModel * m + a]);
+      hm[kSiModel * m + 10] = ok ? 1.0 : 0.0;
+    }
+    MVUS_HIP(hipMemcpyAsync(S->models, hm.data(), sizeof(double) * hm.size(), hipMemcpyHostToDevice, S->st));
+    si_launch_score(S, shift, M, threshold);
+    MVUS_HIP(hipGetLastError());
+    MVUS_HIP(hipMemcpyAsync(counts, S->counts, sizeof(int32_t) * 2 * M, hipMemcpyDeviceToHost, S->st));
+    MVUS_HIP(hipStreamSynchronize(S->st));
     return MVUS_OK;
   });
 }

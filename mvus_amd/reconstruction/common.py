@@ -276,8 +276,16 @@ class Scene:
                 sync_fun = sync.sync_iter
             elif method == 'bf':
                 sync_fun = sync.sync_bf
+            elif method == 'iter_gpu':
+                # the reference's sync_iter on the GPU; settings['sync_iter'] may override its search parameters
+                import functools
+                over = dict(self.settings.get('sync_iter') or {})
+                unknown = set(over) - {'maxIter', 'threshold', 'step', 'p_min', 'p_max', 'seed'}
+                if unknown:
+                    raise ValueError('settings["sync_iter"]: unknown key(s) %s' % sorted(unknown))
+                sync_fun = functools.partial(sync.sync_iter_gpu, **over)
             else:
-                raise ValueError('Synchronization method must be either "iter" or "bf"')
+                raise ValueError('Synchronization method must be "iter", "bf" or "iter_gpu"')
             device = int(self.settings.get('device', 0))
             print('Computing temporal synchronization...\n')
             beta = np.zeros(self.numCam)
