@@ -12,8 +12,9 @@
 #include <string>
 #include <vector>
 
+#include "api_common.h"      // HipError, MVUS_HIP, RoctxRange
 #include "ba_held.h"
-#include "ba_kernels.hip.h"
+#include "ba_kernels.hip.h"      // the umbrella of the evaluation, operator, vector, LSMR, LM-tail and finite-difference kernels: nearly all are launched here
 #include "ba_problem.h"
 #include "ba_solver.h"
 #include "ba_schur.h"

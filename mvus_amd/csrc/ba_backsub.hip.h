@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "ba_kernels.hip.h"
+#include "ba_dev_problem.h"
 #include "ba_ne_views.h"
 #include "ba_partition.h"
 #include "ba_wave.hip.h"

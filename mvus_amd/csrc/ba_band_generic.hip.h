@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_assemble.hip.h"      // ne_diag_grad_entry
+#include "ba_dev_problem.h"
 #include "ba_ne_views.h"
 
 namespace mvus {

@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_band_generic.hip.h"      // band_pack_entry
-#include "ba_kernels.hip.h"
+#include "ba_dev_problem.h"
 #include "ba_ne_views.h"
 #include "ba_partition.h"
 #include "ba_wave.hip.h"

@@ -27,10 +27,13 @@
 // Refusal: a pivot p_k <= kCovPivotTol * H_kk of either factorisation (ba_cov_math.h) -> MVUS_E_NUMERIC naming the unknown.
 #pragma once
 #include <climits>
+#include <cstring>
 
+#include "api_common.h"      // MVUS_HIP
 #include "ba_band_generic.hip.h"
 #include "ba_cov_math.h"
 #include "ba_detcov.hip.h"
+#include "ba_dev_problem.h"
 #include "ba_ne_views.h"
 #include "ba_wave.hip.h"
 

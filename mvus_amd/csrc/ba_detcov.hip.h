@@ -14,7 +14,7 @@
 // the lane that owns the detection.
 #pragma once
 #include "ba_detcov_math.h"
-#include "ba_kernels.hip.h"
+#include "ba_dev_problem.h"
 
 namespace mvus {
 

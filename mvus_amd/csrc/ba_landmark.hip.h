@@ -11,9 +11,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "ba_kernels.hip.h"
+#include "ba_dev_problem.h"
 #include "ba_landmark_math.h"
 #include "ba_ne_views.h"
+#include "ba_wave.hip.h"      // wave_sum
 
 namespace mvus {
 

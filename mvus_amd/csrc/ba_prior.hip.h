@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_assemble.hip.h"      // k_det_motion
-#include "ba_kernels.hip.h"
+#include "ba_dev_problem.h"
 #include "ba_ne_views.h"
 #include "ba_prior_math.h"
 #include "ba_wave.hip.h"

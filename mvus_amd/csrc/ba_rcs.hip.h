@@ -1,6 +1,6 @@
 // Reduced camera system S p_c = -rhs (dense, SPD, nn = C * (3 + P) <= 1152 unknowns): blocked L D L^T with the matrix held in the
-// register layout of the fp64 matrix cores.  NEView and the failure codes come from ba_ne_views.h, d4, lds_wave_sync
-// and ldl_inv16 from ba_wave.hip.h, dpp_shift from ba_kernels.hip.h.
+// register layout of the fp64 matrix cores.  NEView and the failure codes come from ba_ne_views.h, d4, lds_wave_sync,
+// lds_barrier, ldl_inv16 and dpp_shift from ba_wave.hip.h.
 //
 // No counterpart in the reference (Scene.BA hands the whole problem to scipy, reconstruction/common.py:670); this replaces the
 // block Gauss-Jordan of rounds 1-4 (k_gj_step: one launch per 32 columns, 10.1 us each, of which the 32x32 pivot inverse in ONE
@@ -27,7 +27,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "ba_kernels.hip.h"
 #include "ba_ne_views.h"
 #include "ba_wave.hip.h"
 

@@ -4,7 +4,7 @@
 //
 //     evaluate(start)   { round(k) ; evaluate(trial k) }  k = 1 .. max_nfev - 1     round(last)   counts        evaluate = k_cam_states + k_reg_linearize
 //
-//   k_cam_states      (ba_kernels.hip.h, the library's own) decodes the point in flight of every problem -- the batch laid out as the head
+//   k_cam_states      (ba_observe.hip.h, the library's own) decodes the point in flight of every problem -- the batch laid out as the head
 //                     of an x of B cameras -- so that a camera state has the bits it has in every other evaluation of the library.
 //   k_reg_linearize   grid = slabs x problems.  A slab is kRegSlab consecutive detections of the problem's camera, one per lane; the
 //                     partition of a camera depends on its detection count only.  Every lane evaluates its observation at the point in
@@ -27,9 +27,12 @@
 #include <exception>
 #include <vector>
 
+#include "api_common.h"      // MVUS_HIP
 #include "ba_backend.hip.h"
-#include "ba_kernels.hip.h"
+#include "ba_dev_problem.h"
+#include "ba_observe.hip.h"      // k_cam_states
 #include "ba_register_math.h"
+#include "ba_wave.hip.h"         // wave_sum
 
 namespace mvus {
 

@@ -48,7 +48,6 @@
 #include <cstring>
 #include <vector>
 
-#include "ba_kernels.hip.h"
 #include "ba_partition.h"
 #include "ba_gemm_plan.h"
 #include "ba_schur.h"

@@ -1,6 +1,8 @@
 // Host side of the LM + Schur path: HipSchur owns the normal-equation storage, the partition tables, the cost models for the window
 // length and the slab count, and every launch of the kernels behind ba_schur_hip.hip.h (included first: the umbrella of the stage headers, where the device code lives).
 #pragma once
+#include "api_common.h"      // HipError, MVUS_HIP, RoctxRange
+#include "ba_dev_problem.h"
 #include "ba_held.h"
 #include "ba_problem.h"
 #include "ba_schur_hip.hip.h"

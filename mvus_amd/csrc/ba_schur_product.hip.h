@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_gemm_plan.h"
-#include "ba_kernels.hip.h"
 #include "ba_ne_views.h"
 #include "ba_wave.hip.h"
 

@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_band_part.hip.h"      // part_reduce_rhs
-#include "ba_kernels.hip.h"
 #include "ba_ne_views.h"
 #include "ba_partition.h"
 #include "ba_wave.hip.h"

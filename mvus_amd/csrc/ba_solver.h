@@ -275,7 +275,7 @@ inline void intersect_trust_region(const std::vector<double>& x, const std::vect
 
 // ------------------------------------------------------------------------------------------------
 // Scalar state of one LSMR run (scipy lsmr.py:316-470) and its two per-iteration updates, written once for the host loop
-// and for the HIP backend's device-resident loop (k_lsmr_* in ba_kernels.hip.h), which runs whole batches of iterations
+// and for the HIP backend's device-resident loop (k_lsmr_* in ba_lsmr.hip.h), which runs whole batches of iterations
 // without a host round trip.  No FMA contraction in here: host and device then produce the same bits.
 // ------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)

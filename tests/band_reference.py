@@ -1,4 +1,4 @@
-"""Reference for the spline fit's band solvers (k_band_solve, k_band_solve_parts, k_band_diag_sum of mvus_amd/csrc/spline_fit.hip.h,
+"""Reference for the spline fit's band solvers (k_band_solve, k_band_solve_parts, k_band_diag_sum of mvus_amd/csrc/spline_band_solve*.hip.h,
 reached through mvus_spline_band_solve / mvus_spline_band_diag_sum): seeded systems with a known factor, a banded Cholesky solve in
 mpmath at 50 digits, and the list of cases tests/test_gpu_band_solve.py runs -- tests/test_band_solve_host.py asserts the premises of
 every system on that list without a GPU.

@@ -1,6 +1,6 @@
 """Reference for the passes of the smoothing fit around its band solvers (k_fit_basis, k_fit_first, k_fit_blocks, k_fit_slice_sum,
 k_fit_band, k_fit_penalty, k_fit_residual, k_fit_total_partial / k_fit_total, k_fit_fpint / k_fit_fpint_final of
-mvus_amd/csrc/spline_fit.hip.h, reached through mvus_spline_fit_normal / _penalty / _residual): exact sums in rational arithmetic of
+mvus_amd/csrc/spline_fit_passes.hip.h, reached through mvus_spline_fit_normal / _penalty / _residual): exact sums in rational arithmetic of
 exactly what a kernel was given, the basis by de Boor's recurrence at 50 digits, and the list of cases tests/test_gpu_fit_passes.py runs.
 Host only: nothing here comes from the GPU; tests/test_fit_passes_host.py asserts the premises of every case and holds this module to
 scipy and to oracle/fitpack_oracle.py.

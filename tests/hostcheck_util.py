@@ -1,5 +1,6 @@
 """Build/load the TEST-ONLY host build of the device math + optimiser (tests/hostcheck)."""
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -10,8 +11,9 @@ from mvus_amd import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = [os.path.join(HERE, 'hostcheck', f) for f in ('hostcheck.cpp', 'host_backend.cpp')]
-DEPS = SRC + [os.path.join(ROOT, 'mvus_amd', 'csrc', f) for f in ('ba_math.h', 'ba_switches.h', 'ba_solver.h', 'ba_held.h', 'ba_problem.h', 'ba_schur.h', 'ba_partition.h', 'triangulate.hip.h', 'spline_fit.hip.h', 'pnp.hip.h', 'epipolar.hip.h')] \
-    + [os.path.join(ROOT, 'include', 'mvus_ba.h')]
+DEPS = SRC + [os.path.join(ROOT, 'mvus_amd', 'csrc', f) for f in ('ba_math.h', 'ba_switches.h', 'ba_solver.h', 'ba_held.h', 'ba_problem.h', 'ba_schur.h', 'ba_partition.h', 'triangulate.hip.h', 'pnp.hip.h', 'epipolar.hip.h')] \
+    + sorted(glob.glob(os.path.join(ROOT, 'mvus_amd', 'csrc', 'spline_*.h'))) \
+    + [os.path.join(ROOT, 'include', 'mvus_ba.h')]      # (spline_fit.hip.h is an umbrella: the host build reads the headers behind it)
 SO = os.path.join(HERE, 'hostcheck', 'libhostcheck.so')
 
 _cached = None

@@ -19,7 +19,7 @@ JT_WIN = 144       # kJtWin: control points per chunk window of the J^T u gather
 
 
 def xcd_grid(tiles):
-    """workgroups launched for ``tiles`` chunks (xcd_grid of ba_kernels.hip.h): whole runs on all eight XCDs"""
+    """workgroups launched for ``tiles`` chunks (xcd_grid of ba_dev_problem.h): whole runs on all eight XCDs"""
     run = min(64, max(1, (tiles + 7) // 8))
     per = 8 * run
     return (tiles + per - 1) // per * per

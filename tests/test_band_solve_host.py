@@ -1,6 +1,6 @@
 """What tests/test_gpu_band_solve.py rests on, checked without a GPU: the premises of every system it hands to the band solvers (from
 the 50-digit factor: these are conditions, not measurements), the reference against LAPACK, and the invariants of the partition
-(band_parts / band_parts_fixed of mvus_amd/csrc/spline_fit.hip.h through the host build) for every n the fit can reach in the tests."""
+(band_parts / band_parts_fixed of mvus_amd/csrc/spline_band_parts.h through the host build) for every n the fit can reach in the tests."""
 import ctypes
 
 import numpy as np

@@ -1,5 +1,5 @@
 """What tests/test_gpu_fit_passes.py rests on, checked without a GPU: the capacities of the fit's sliced passes and of its two-stage
-total (fit_slices, kFitSliceBlocks, kFitBlk, fit_total_parts of mvus_amd/csrc/spline_fit.hip.h through the host build), the reference
+total (fit_slices, kFitSliceBlocks, kFitBlk, fit_total_parts of mvus_amd/csrc/spline_fit_passes.hip.h through the host build), the reference
 of tests/fit_reference.py against scipy and oracle/fitpack_oracle.py, the premises of every case, and what the entry points refuse."""
 import ctypes
 from fractions import Fraction

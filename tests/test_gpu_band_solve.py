@@ -1,4 +1,4 @@
-"""The spline fit's band solvers -- k_band_solve, k_band_solve_parts, k_band_diag_sum (mvus_amd/csrc/spline_fit.hip.h), HB = 3 and 4, fp64
+"""The spline fit's band solvers -- k_band_solve, k_band_solve_parts, k_band_diag_sum (mvus_amd/csrc/spline_band_solve*.hip.h), HB = 3 and 4, fp64
 and double-double -- on their own, through mvus_spline_band_solve / mvus_spline_band_diag_sum, against a banded Cholesky solve at 50
 digits (tests/band_reference.py: the systems, their families A .. E and the genuine pair 'G', and the list of shapes; their premises
 are asserted by tests/test_band_solve_host.py).

@@ -1,6 +1,6 @@
 """The passes of the smoothing fit around its band solvers -- k_fit_basis, k_fit_first, k_fit_blocks<T, NT>, k_fit_slice_sum<T>,
 k_fit_band<T>, k_fit_penalty<T>, k_fit_residual, k_fit_total_partial / k_fit_total, k_fit_fpint / k_fit_fpint_final
-(mvus_amd/csrc/spline_fit.hip.h) -- on their own, through mvus_spline_fit_normal / _penalty / _residual, each against an exact
+(mvus_amd/csrc/spline_fit_passes.hip.h) -- on their own, through mvus_spline_fit_normal / _penalty / _residual, each against an exact
 (rational) reference of exactly what it was given (tests/fit_reference.py: the cases, the chain lengths k and where they come from;
 tests/test_fit_passes_host.py asserts the premises of the cases).  fp64 (NT = 256) and double-double (NT = 64) throughout.
 

@@ -1,5 +1,5 @@
 """The weighted smoothing fit -- splprep's ``w`` through mvus_spline_smooth_w / mvus_spline_fit_open_w and the two kernels that read the
-weights, k_fit_blocks_w<T, NT> and k_fit_residual_w (mvus_amd/csrc/spline_fit.hip.h):
+weights, k_fit_blocks_w<T, NT> and k_fit_residual_w (mvus_amd/csrc/spline_fit_weighted.hip.h):
 
   1. the weighted fit is FITPACK's: scipy's ``splprep(w=...)`` is the reference (oracle/fitpack_oracle.py is unit-weight) -- identical
      knots and ier, fp to 1e-8 max(fp, s), coefficients within max(1e-8, 8 x spread), ``spread`` the largest change of scipy's OWN weighted

@@ -98,7 +98,7 @@ def test_oracle_reproduces_the_reference_fixture():
 
 
 def test_host_side_of_the_gpu_fit_matches_the_oracle():
-    """The scalar FITPACK routines the GPU path runs on the host (csrc/spline_fit.hip.h: fpdisc, fprati, fpknot), compiled with
+    """The scalar FITPACK routines the GPU path runs on the host (csrc/spline_fitpack_host.h: fpdisc, fprati, fpknot), compiled with
     g++ (tests/hostcheck), against the oracle's restatement -- bit for bit, they are the same arithmetic."""
     import ctypes
     from hostcheck_util import load
