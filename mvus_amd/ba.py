@@ -26,6 +26,20 @@ def loss_code(loss):
     return int(loss)
 
 
+def _weights(sigma, rows, K, what):
+    """sigma as a scalar, per axis (rows,) or per axis and element (rows, K) -> contiguous (rows, K) weights 1 / sigma, 0 for an infinite sigma."""
+    s = np.asarray(sigma, dtype=np.float64)
+    if s.ndim == 1 and s.shape == (rows,):
+        s = s[:, None]
+    elif s.ndim not in (0, 2) or (s.ndim == 2 and s.shape != (rows, K)):
+        raise ValueError('%s: sigma has shape %s, expected a scalar, (%d,) or (%d, %d)' % (what, s.shape, rows, rows, K))
+    s = np.broadcast_to(s, (rows, K))
+    if np.any(np.isnan(s)) or np.any(s <= 0):
+        raise ValueError('%s: sigma must be positive (np.inf leaves an axis out)' % what)
+    with np.errstate(divide='ignore'):
+        return np.ascontiguousarray(np.where(np.isinf(s), 0.0, 1.0 / s))
+
+
 def position_prior_arrays(t, P, sigma):
     """(t (K,), P (3, K), sigma scalar | (3,) | (3, K)) -> contiguous float64 (t, P, w) with w = 1 / sigma (0 for an infinite sigma).
     Shapes, NaN and non-positive sigma raise ValueError here; the library checks the numbers again."""
@@ -33,17 +47,7 @@ def position_prior_arrays(t, P, sigma):
     P = np.ascontiguousarray(P, dtype=np.float64)
     if P.shape != (3, t.size):
         raise ValueError('position priors: P has shape %s, expected (3, %d)' % (P.shape, t.size))
-    s = np.asarray(sigma, dtype=np.float64)
-    if s.ndim == 1 and s.shape == (3,):
-        s = s[:, None]
-    elif s.ndim not in (0, 2) or (s.ndim == 2 and s.shape != (3, t.size)):
-        raise ValueError('position priors: sigma has shape %s, expected a scalar, (3,) or (3, %d)' % (s.shape, t.size))
-    s = np.broadcast_to(s, (3, t.size))
-    if np.any(np.isnan(s)) or np.any(s <= 0):
-        raise ValueError('position priors: sigma must be positive (np.inf leaves an axis out)')
-    with np.errstate(divide='ignore'):
-        w = np.ascontiguousarray(np.where(np.isinf(s), 0.0, 1.0 / s))
-    return t, P, w
+    return t, P, _weights(sigma, 3, t.size, 'position priors')
 
 
 def landmark_arrays(X, cam, point, uv, sigma):
@@ -59,17 +63,7 @@ def landmark_arrays(X, cam, point, uv, sigma):
     uv = np.ascontiguousarray(uv, dtype=np.float64)
     if point.size != K or uv.shape != (2, K):
         raise ValueError('landmarks: cam (%d,), point (%d,) and uv %s do not describe the same K observations' % (K, point.size, uv.shape))
-    s = np.asarray(sigma, dtype=np.float64)
-    if s.ndim == 1 and s.shape == (2,):
-        s = s[:, None]
-    elif s.ndim not in (0, 2) or (s.ndim == 2 and s.shape != (2, K)):
-        raise ValueError('landmarks: sigma has shape %s, expected a scalar, (2,) or (2, %d)' % (s.shape, K))
-    s = np.broadcast_to(s, (2, K))
-    if np.any(np.isnan(s)) or np.any(s <= 0):
-        raise ValueError('landmarks: sigma must be positive (np.inf leaves an axis out)')
-    with np.errstate(divide='ignore'):
-        w = np.ascontiguousarray(np.where(np.isinf(s), 0.0, 1.0 / s))
-    return X, cam, point, uv, w
+    return X, cam, point, uv, _weights(sigma, 2, K, 'landmarks')
 
 
 class UnsupportedBySolver(RuntimeError):
@@ -96,6 +90,10 @@ class _Result(SimpleNamespace):
 
 
 class BAHandle:
+    # in force on the handle: what set_loss / set_frozen / set_position_priors / set_landmarks last sent and the library accepted
+    loss, _frozen, _position_priors, _landmarks = (LOSS_LINEAR, 1.0), None, None, None
+    _KEEP = object()                   # configure: "leave this as it is" (None already means "clear")
+
     def __init__(self, prob, device=0, stream=None):
         self.lib = _lib.load()
         self.prob = prob
@@ -111,8 +109,6 @@ class BAHandle:
         self.NS = int(self.lib.mvus_ba_num_slots(h))
         self.M = prob.M
         self._cb = None
-        self.loss = (LOSS_LINEAR, 1.0)     # (code, f_scale) in force: set_loss
-        self._frozen = None                # mask in force: set_frozen
 
     def close(self):
         if getattr(self, 'h', None):
@@ -328,9 +324,13 @@ class BAHandle:
         over remove_outliers.  ``t = None`` (or K = 0) clears them.  Priors outside every interval of the spline are inactive."""
         if t is None or np.size(t) == 0:
             self._check(self.lib.mvus_ba_set_position_priors(self.h, 0, None, None, None), 'mvus_ba_set_position_priors')
+            self._position_priors = None
             return
-        t, P, w = position_prior_arrays(t, P, sigma)
-        self._check(self.lib.mvus_ba_set_position_priors(self.h, t.size, _lib.dptr(t), _lib.dptr(P), _lib.dptr(w)), 'mvus_ba_set_position_priors')
+        tc, Pc, w = position_prior_arrays(t, P, sigma)
+        self._check(self.lib.mvus_ba_set_position_priors(self.h, tc.size, _lib.dptr(tc), _lib.dptr(Pc), _lib.dptr(w)), 'mvus_ba_set_position_priors')
+        self._position_priors = tuple(np.array(a, dtype=np.float64) for a in (t, P, sigma))
+
+    position_priors = property(lambda self: self._position_priors, doc='(t, P, sigma) as last sent (copies), or None without priors')
 
     @property
     def num_position_priors(self):
@@ -359,10 +359,29 @@ class BAHandle:
         remove_outliers.  ``X = None`` (or K = 0) clears them."""
         if X is None or cam is None or np.size(cam) == 0:
             self._check(self.lib.mvus_ba_set_landmarks(self.h, 0, None, 0, None, None, None, None), 'mvus_ba_set_landmarks')
+            self._landmarks = None
             return
-        X, cam, point, uv, w = landmark_arrays(X, cam, point, uv, sigma)
-        self._check(self.lib.mvus_ba_set_landmarks(self.h, X.shape[1], _lib.dptr(X), cam.size, cam.ctypes.data_as(_lib.c_int32_p),
-                                                   point.ctypes.data_as(_lib.c_int32_p), _lib.dptr(uv), _lib.dptr(w)), 'mvus_ba_set_landmarks')
+        Xc, camc, pointc, uvc, w = landmark_arrays(X, cam, point, uv, sigma)
+        self._check(self.lib.mvus_ba_set_landmarks(self.h, Xc.shape[1], _lib.dptr(Xc), camc.size, camc.ctypes.data_as(_lib.c_int32_p),
+                                                   pointc.ctypes.data_as(_lib.c_int32_p), _lib.dptr(uvc), _lib.dptr(w)), 'mvus_ba_set_landmarks')
+        self._landmarks = tuple(np.array(a) for a in (X, cam, point, uv, sigma))
+
+    landmarks = property(lambda self: self._landmarks, doc='(X, cam, point, uv, sigma) as last sent (copies), or None without landmarks')
+
+    def configure(self, loss=_KEEP, frozen=_KEEP, position_priors=_KEEP, landmarks=_KEEP):
+        """Make the state of the handle what is given -- ``loss`` (code, f_scale), ``frozen`` a mask, ``position_priors`` / ``landmarks`` the arguments of
+        their ``set_*``; None clears the last three; what is not given is left alone.  A ``set_*`` is called only where the state differs: a
+        redundant one would drop what the last LM solve carried over, a changed one resets the damping."""
+        if loss is not self._KEEP and tuple(loss) != self.loss:
+            self.set_loss(*loss)
+        cur = self.frozen                      # (no mask and an all-false mask are the same state)
+        if frozen is not self._KEEP and (np.any(frozen) if cur is None else frozen is None or not np.array_equal(frozen, cur)):
+            self.set_frozen(frozen)
+        for new, cur, setter in ((position_priors, self._position_priors, self.set_position_priors), (landmarks, self._landmarks, self.set_landmarks)):
+            if new is None and cur is not None:
+                setter(*[None] * len(cur))
+            elif new is not None and new is not self._KEEP and not (cur is not None and all(np.array_equal(a, b) for a, b in zip(cur, new))):
+                setter(*new)                   # (array_equal: the element counts first, then every number)
 
     @property
     def num_landmark_observations(self):

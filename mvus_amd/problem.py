@@ -124,7 +124,6 @@ class BAProblem:
             K=self.K, dist=self.dist, interval=self.interval, knot_offsets=self.knot_offsets,
             knots=self.knots, opt_sync=self.opt_sync), keep
 
-
     # ---- time sharding --------------------------------------------------------------------------
     def detection_spans(self, x):
         """Global index of the first of the four control points each detection touches at parameters ``x``
@@ -214,6 +213,28 @@ def problem_from_arrays(detections, cameras, tck, interval, *, opt_calib=False, 
         v_raw=np.ascontiguousarray(det[2]), img_height=H, K=K, dist=dist,
         interval=np.ascontiguousarray(np.asarray(interval, dtype=np.float64)),
         knot_offsets=koff, knots=np.concatenate(knots) if knots else np.zeros(0), opt_sync=bool(opt_sync))
+
+
+class HeadLayout:
+    """The camera-side head of x for C cameras, in pack_x order: alpha(C), beta(C), rs(C), then P parameters per camera in
+    Camera.P2vector order -- K | R | t | d (fx fy cx cy | rvec | t | k1 k2 p1 p2 k3) with ``calib``, else R | t."""
+    HEAD = ('alpha', 'beta', 'rs')
+
+    def __init__(self, calib, C=1):
+        self.C = int(C)
+        self.part = {'K': range(0, 4), 'R': range(4, 7), 't': range(7, 10), 'd': range(10, 15)} if calib else {'R': range(0, 3), 't': range(3, 6)}
+        self.names = (['fx', 'fy', 'cx', 'cy'] if calib else []) + ['r1', 'r2', 'r3', 't1', 't2', 't3'] + (['k1', 'k2', 'p1', 'p2', 'k3'] if calib else [])
+        self.P, self.size = len(self.names), self.C * (3 + len(self.names))
+
+    def index(self, k, what):
+        """Where camera k's 'alpha' | 'beta' | 'rs', its parameter called ``what`` or its parameter number ``what`` stands."""
+        if what in self.HEAD:
+            return self.HEAD.index(what) * self.C + k
+        return 3 * self.C + k * self.P + (self.names.index(what) if isinstance(what, str) else int(what))
+
+    def indices(self, k, name):
+        """Every index of camera k that the ``ba_freeze`` name 'alpha' | 'beta' | 'rs' | 'K' | 'R' | 't' | 'd' covers (K, d without ``calib``: none)."""
+        return [self.index(k, name)] if name in self.HEAD else [self.index(k, j) for j in self.part.get(name, ())]
 
 
 def pack_x(prob, alpha, beta, rs, cameras, tck):

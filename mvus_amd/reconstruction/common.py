@@ -10,64 +10,8 @@ side effects of ``BA`` on ``alpha/beta/rs/cameras/spline/detections_global``.
 Also on the GPU: ``Scene.init_traj`` (two-view initialisation: fundamental matrix by RANSAC, optimal correction, pose from
 E), ``Scene.time_shift`` with ``cf_exact: false`` and ``sync_method: 'bf'`` (synchronization.sync_bf), ``get_camera_pose`` (PnP +
 RANSAC) and ``Scene.triangulate`` (per-point SVD).  Out of scope: ``sync_iter``, plotting, and the dead ``motion_prior=True``
-branch -- those raise ``NotImplementedError``.
-
-Extra ``settings`` keys (all optional; a reference ``config.json`` has none of them):
-
-``ba_solver``  'trf' (DEFAULT) = scipy's TRF + LSMR restated on the GPU -- with ``ba_jacobian`` 'fd' (its default) this is
-               the reference's algorithm end to end: same pattern matrix, same grouped 2-point differences, same trust
-               region, same termination; results agree with the reference's within the reference's own reproducibility.
-               'lm' = Levenberg-Marquardt on device-assembled normal equations with the Schur complement and the analytic
-               Jacobian: ~20x faster per BA iteration, reaches a LOWER value of the same objective, hence another point than
-               the reference's (DESIGN.md section 2 states how far, against the reference and against ground truth).
-``ba_jacobian`` 'fd' (default with 'trf'), 'pattern' = analytic, masked to the reference sparsity pattern, 'analytic' =
-               full analytic (default with 'lm').
-``ba_pattern_ties`` 'numpy' = the twin rows of the pattern decided like np.argsort of this process decides them (default;
-               what the reference would build here), 'canonical'.
-``ba_lambda_min`` floor of the LM damping (default 3e-3, see ``mvus_solve_opts.lm_lambda_min``; the incremental loop of
-               ``mvus_amd.pipeline`` sets 0.3 for its staged BAs unless told otherwise: ``LOOP_LM_LAMBDA_MIN`` below).
-``ba_lm_wide_band`` with 'lm': what to do when the motion rows reach over more than six control points (knots less than a frame
-               apart, i.e. more control points than detections): 'trf' (default) solves THAT problem with TRF + LSMR on the analytic
-               Jacobian and says so, 'lm' keeps LM + Schur (general band solver, damping floor 0.3).
-``ba_loss``, ``ba_f_scale`` with 'lm': the ``loss`` ('linear' DEFAULT, 'soft_l1', 'huber', 'cauchy', 'arctan') and ``f_scale`` (default 1.0,
-               pixels) arguments of scipy's least_squares, which the reference never passes: gross outliers stop pulling on the first
-               BA, the one that runs before ``remove_outliers`` can cut them.  Not with 'trf' (ValueError), and a problem the
-               wide-band policy above would hand to TRF raises instead of dropping the loss.
-``ba_freeze``  {camera index: [names]} with names from 'alpha', 'beta', 'rs', 'R', 't', 'K', 'd': those parameters of that camera are held
-               constant during BA (``mvus_ba_set_frozen``; both solvers).  'K' and 'd' need ``opt_calib`` (they are not parameters
-               otherwise); cameras outside the BA's ``sequence[:numCam]`` are ignored for that BA.  The reference can only switch a
-               group off for every camera at once (``opt_sync``, ``rs``, ``opt_calib``).
-``ba_gauge``   'free' (DEFAULT: the reference's problem, similarity gauge left to the solver) or 'anchor': the pose of ``sequence[0]`` and
-               one translation component of ``sequence[1]`` are held -- the seven degrees of freedom of the similarity, no more
-               (``Scene.ba_frozen_mask``).
-``ba_covariance`` True: ``mvus_amd.pipeline.reconstruct_from_config`` calls ``Scene.ba_covariance`` after the last BA and the output pickle carries
-               its dict (``Scene.covariance``).  DEFAULT False: nothing changes.  Needs a fixed gauge (``ba_gauge: 'anchor'`` or ``ba_freeze``).
-``ba_detection_covariance`` True: ``reconstruct_from_config`` calls ``Scene.ba_detection_covariance`` after the last BA (one call that also yields
-               ``Scene.covariance`` when ``ba_covariance`` is on) and the output pickle carries its dict (``Scene.detection_covariance``): per
-               detection the signed residual, the 1-sigma ellipse of the fitted detection and the studentised residual.  DEFAULT False.
-``ba_kinematics`` True: ``reconstruct_from_config`` calls ``Scene.kinematics`` after ``spline_to_traj`` (after ``Scene.ba_covariance``, with its band, when
-               ``ba_covariance`` is on too) and the output pickle carries its dict.  DEFAULT False: nothing changes.
-``ba_landmarks`` True with 'lm': ``Scene.landmarks`` (3, L) -- surveyed static points -- and ``Scene.landmark_observations`` (6, K): camera id,
-               landmark, u, v, sigma_u, sigma_v -- enter ``Scene.BA`` as observations (``mvus_ba_set_landmarks``): two rows per click that
-               involve the clicked camera only and fix the similarity gauge, scale included.  ``reconstruct_from_config`` runs the
-               incremental loop as without them, then moves the result into the surveyed frame (``Scene.align_to_landmarks``) and ends
-               with one LM BA over all cameras that carries them.  Not with 'trf' (ValueError); a problem the wide-band policy above
-               would hand to TRF raises; ``register_camera`` raises while the setting is on and the scene holds landmarks.  DEFAULT false.
-``ba_position_priors`` True with 'lm': ``Scene.position_priors`` -- surveyed positions (a GPS / RTK log) as a (7, K) array of t, x, y, z, sigma_x,
-               sigma_y, sigma_z on the spline's timeline -- enter ``Scene.BA`` as observations (``mvus_ba_set_position_priors``): three
-               non-collinear ones fix the similarity gauge, and the trajectory, the poses and their covariance come out in the surveyed
-               frame, in its unit.  ``reconstruct_from_config`` then runs its loop as always, aligns the scene to the priors
-               (``Scene.align_to_position_priors``) and ends with one LM BA over all cameras that carries them.  Not with 'trf'
-               (ValueError), and a problem the wide-band policy above would hand to TRF raises instead of dropping the priors.  DEFAULT
-               False: nothing changes.
-``ba_register`` True: the incremental loop of ``mvus_amd.pipeline`` calls ``Scene.register_camera`` on every new camera between
-               ``get_camera_pose`` and ``triangulate``: alpha, beta, rs and the pose of THAT camera are adjusted against the trajectory as it
-               stands (``mvus_ba_register_cameras``: Levenberg-Marquardt per camera on the device), the spline and the other cameras
-               untouched.  ``ba_register_beta_search`` [half_width, step] (frames, optional) makes it start from beta + k step,
-               |k step| <= half_width, all in one call, and keep the start with the most inliers.  DEFAULT False: nothing changes.
-``ba_deterministic`` accepted and ignored: the 'lm' solver's normal equations are assembled without floating-point atomics
-               (one writer, one order of additions per entry) -- the same bits on every run by construction.
-``opt_sync`` (reference key: False freezes alpha/beta), ``device``.
+branch -- those raise ``NotImplementedError``.  The optional ``settings`` keys this package adds (``ba_*``; a reference ``config.json``
+has none of them) are listed, documented and validated in ``ba_settings.py``.
 """
 import json
 
@@ -76,6 +20,8 @@ import numpy as np
 from ..tools import util
 from .. import problem as _problem
 from ..synth import rodrigues as _rodrigues, rotation_to_rvec as _rotation_to_rvec
+from . import ba_settings as _settings
+from .surveyed import check_landmarks, check_position_priors, load_landmarks, load_position_priors, umeyama_similarity, _undistort_normalised  # noqa: F401
 
 
 def _undistort_normalized(points, K, d):
@@ -335,7 +281,7 @@ class Scene:
         from .. import spline as _spline
         assert len(smooth_factor) == 2, 'Smoothness should be defined by two parameters (min, max)'
         interval, idx = util.find_intervals(self.traj[0], idx=True)
-        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
+        device = self._device()
         sigma = getattr(self, 'traj_sigma', None)
         # traj_sigma counts only while it is aligned with traj: code that cuts or reorders self.traj by hand (s.traj = s.traj[:, mask]) and
         # does not cut traj_sigma with it gets the unweighted fit, said aloud -- sigmas of other samples would be worse than none
@@ -356,19 +302,7 @@ class Scene:
         'triangulation' -- ``init_traj`` and ``triangulate`` then keep the 1-sigma of every triangulated point in ``traj_sigma``
         (``triangulate_with_cov`` with ``settings['traj_sigma_px']`` pixels of noise: a scalar or one value per camera, default 1) and
         ``traj_to_spline`` fits with w = max(sigma_min / sigma, ``settings['traj_weight_floor']``) (default 1e-3)."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        mode = st.get('traj_weights')
-        if mode is None:
-            return None
-        if mode != 'triangulation':
-            raise ValueError("settings['traj_weights'] must be 'triangulation' or absent, not %r" % (mode,))
-        px = np.asarray(st.get('traj_sigma_px', 1.0), dtype=np.float64)
-        if px.ndim > 1 or (px.ndim == 1 and px.size != self.numCam) or not np.all(np.isfinite(px)) or not np.all(px > 0):
-            raise ValueError("settings['traj_sigma_px'] must be a positive number, or one per camera")
-        floor = float(st.get('traj_weight_floor', 1e-3))
-        if not (0.0 < floor <= 1.0):
-            raise ValueError("settings['traj_weight_floor'] must lie in (0, 1]")
-        return mode, np.broadcast_to(px, (self.numCam,)), floor
+        return _settings.traj_weights(_settings.as_dict(self.settings), self.numCam)
 
     @staticmethod
     def weights_from_sigma(sigma, floor=1e-3):
@@ -397,8 +331,7 @@ class Scene:
             ts = np.asarray(t, dtype=np.float64)
         else:
             ts = np.arange(interval[0, 0], interval[1, -1], sampling_rate)
-        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
-        X, which = _spline.evaluate(tck, interval, ts, device=device)
+        X, which = _spline.evaluate(tck, interval, ts, device=self._device())
         parts = [np.empty([4, 0])]
         for i in range(interval.shape[1]):                       # the reference's order: interval by interval
             m = which == i
@@ -413,8 +346,7 @@ class Scene:
         """Attributes the reference refreshes while regularising (common.py:887-947); they do not enter the
         residual, so they are computed once after BA instead of on every evaluation."""
         cams = list(cam[0]) if len(cam) else list(range(self.numCam))
-        for i in cams:
-            self.detection_to_global(i)
+        self.detection_to_global(cams)
         ts = np.concatenate([self.detections_global[i][0] for i in cams])
         frames = np.concatenate([self.detections[i][0] for i in cams])
         ids = np.concatenate([np.full(self.detections[i].shape[1], float(i)) for i in cams])
@@ -440,9 +372,12 @@ class Scene:
         return _problem.pack_x(prob, np.asarray(self.alpha)[cams], np.asarray(self.beta)[cams], np.asarray(self.rs)[cams],
                                [self.cameras[i] for i in cams], self.spline['tck'])
 
+    def _device(self):
+        return int(_settings.as_dict(self.settings).get('device', 0))
+
     def _handle(self, prob):
         from ..ba import BAHandle          # raises if libmvusba.so is missing: no CPU fallback
-        return BAHandle(prob, device=int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0)
+        return BAHandle(prob, device=self._device())
 
     @staticmethod
     def _same_problem(a, b):
@@ -464,6 +399,12 @@ class Scene:
             h.close()
         self._ba_handle, self._ba_key = self._handle(prob), tuple(cams)
         return self._ba_handle
+
+    def _configured_handle(self, prob, cams):
+        """``_resident_handle`` with the loss, the held parameters, the position priors and the landmarks of the settings in force (sent only where they differ)."""
+        h = self._resident_handle(prob, cams)
+        h.configure(loss=self.ba_loss(), frozen=self.ba_frozen_mask(cams), position_priors=self.ba_position_priors(), landmarks=self.ba_landmarks(cams))
+        return h
 
     def _resident_for(self, cams):
         """The handle left by the last BA if it still describes the CURRENT scene state of its cameras (detections, knots,
@@ -553,21 +494,8 @@ class Scene:
         print('Doing BA with {} cameras...\n'.format(numCam))
         st = self.settings
         solver, jac_mode = self.ba_mode()
-        loss, f_scale = self.ba_loss()
-        h = self._resident_handle(prob, cams)      # stays resident for remove_outliers and the next BA
-        if h.loss != (loss, f_scale):              # (a handle that has the loss already keeps what its last solve carried over)
-            h.set_loss(loss, f_scale)
-        if 'ba_freeze' in st or 'ba_gauge' in st or h.num_frozen:
-            # held parameters (ba_freeze, ba_gauge): state of the handle like the loss, so the TRF hand-over below solves with them too
-            mask, cur = self.ba_frozen_mask(cams), h.frozen
-            if not np.array_equal(mask, cur if cur is not None else np.zeros(mask.size, dtype=bool)):
-                h.set_frozen(mask)
-        priors = self.ba_position_priors()
-        self._apply_position_priors(h, priors)
-        self._apply_landmarks(h, self.ba_landmarks(cams))
-        opts = _ba._lib.default_opts(solver, jac_mode, max_iter)
-        opts.lm_lambda_min = float(st.get('ba_lambda_min', opts.lm_lambda_min))
-        opts.lm_trust_radius = float(st.get('ba_trust_radius', opts.lm_trust_radius))
+        h = self._configured_handle(prob, cams)    # stays resident for remove_outliers and the next BA
+        opts = _settings.solve_options(st, solver, jac_mode, max_iter)
         try:
             if solver == _ba.SOLVER_LM_SCHUR and st.get('ba_lm_wide_band', 'trf') != 'lm' and self._motion_band_width(prob) > 6:
                 # POLICY, not a limit of the library (it solves bands of up to sixteen control points, tests/test_gpu_schur.py): knots less
@@ -579,19 +507,13 @@ class Scene:
             res = h.solve(model, opts=opts, ties=st.get('ba_pattern_ties', 'numpy'), matrix=jac_sparsity)
             res.solver_used = 'lm' if solver == _ba.SOLVER_LM_SCHUR else 'trf'
         except _ba.UnsupportedBySolver as e:
-            if loss != _ba.LOSS_LINEAR:
-                # the other solver has no robust loss: handing the problem over would silently solve the linear one
-                raise _ba.UnsupportedBySolver("settings['ba_loss'] = %r needs the LM solver, which does not take this problem (%s); the fallback "
-                                              "to ba_solver=trf would drop the loss -- set ba_lm_wide_band: 'lm' or ba_loss: 'linear'"
-                                              % (st.get('ba_loss'), e)) from e
-            if h.num_active_position_priors:
-                # nor position priors: never solved with them dropped
-                raise _ba.UnsupportedBySolver("settings['ba_position_priors'] needs the LM solver, which does not take this problem (%s); the fallback "
-                                              "to ba_solver=trf would drop the priors -- set ba_lm_wide_band: 'lm' or ba_position_priors: false" % (e,)) from e
-            if h.num_landmark_rows:
-                # nor landmarks
-                raise _ba.UnsupportedBySolver("settings['ba_landmarks'] needs the LM solver, which does not take this problem (%s); the fallback "
-                                              "to ba_solver=trf would drop the landmarks -- set ba_lm_wide_band: 'lm' or ba_landmarks: false" % (e,)) from e
+            # the other solver has no robust loss, no position priors and no landmarks: handing the problem over would silently solve without them
+            for on, key, what, off in ((h.loss[0] != _ba.LOSS_LINEAR, "ba_loss'] = %r" % (st.get('ba_loss'),), 'loss', "ba_loss: 'linear'"),
+                                       (h.num_active_position_priors, "ba_position_priors']", 'priors', 'ba_position_priors: false'),
+                                       (h.num_landmark_rows, "ba_landmarks']", 'landmarks', 'ba_landmarks: false')):
+                if on:
+                    raise _ba.UnsupportedBySolver("settings['%s needs the LM solver, which does not take this problem (%s); the fallback to ba_solver=trf "
+                                                  "would drop the %s -- set ba_lm_wide_band: 'lm' or %s" % (key, e, what, off)) from e
             # LM + Schur keeps the spline block as a band of at most sixteen 3x3 blocks (MVUS_E_UNSUPPORTED beyond; FITPACK knots far
             # below one frame apart make the motion rows reach further).  The other GPU solver has no such limit: same analytic
             # Jacobian, TRF + LSMR instead of the normal equations.  Said aloud and recorded in the result, not silently.
@@ -622,42 +544,19 @@ class Scene:
     def ba_mode(self):
         """(solver, Jacobian mode) that ``BA`` runs with the current settings.  Without any ``ba_*`` key -- a reference
         config.json -- that is the reference's own algorithm: TRF + LSMR over grouped 2-point differences."""
-        from .. import ba as _ba
-        st = self.settings if isinstance(self.settings, dict) else {}
-        name = st.get('ba_solver', 'trf')
-        if name not in ('trf', 'lm'):
-            raise ValueError("settings['ba_solver'] must be 'trf' or 'lm', not %r" % (name,))
-        solver = _ba.SOLVER_LM_SCHUR if name == 'lm' else _ba.SOLVER_TRF_LSMR
-        default_jac = 'analytic' if name == 'lm' else 'fd'
-        modes = {'analytic': _ba.JAC_ANALYTIC, 'pattern': _ba.JAC_PATTERN, 'fd': _ba.JAC_FD}
-        jac = st.get('ba_jacobian', default_jac)
-        if jac not in modes:
-            raise ValueError("settings['ba_jacobian'] must be one of %s, not %r" % (sorted(modes), jac))
-        self.ba_loss()                       # (validated with the rest: a bad ba_loss / ba_f_scale raises before any GPU call)
-        self.ba_freeze()                     # (and ba_freeze / ba_gauge)
-        self.ba_covariance_enabled()         # (and ba_covariance)
-        self.ba_kinematics_enabled()         # (and ba_kinematics)
-        self.ba_detection_covariance_enabled()      # (and ba_detection_covariance)
-        self.ba_register_enabled()           # (and ba_register / ba_register_beta_search)
-        self.ba_register_beta_search()
-        self.ba_position_priors()            # (and ba_position_priors / Scene.position_priors)
-        self.ba_landmarks()                  # (and ba_landmarks / Scene.landmarks / Scene.landmark_observations)
-        return solver, modes[jac]
+        st = _settings.as_dict(self.settings)
+        _settings.validate(st)               # every ba_* key of the table: a bad one raises before any GPU call
+        self.ba_position_priors()            # (and the arrays they switch on: Scene.position_priors,
+        self.ba_landmarks()                  # Scene.landmarks / Scene.landmark_observations)
+        return _settings.solver_and_jacobian(st)
 
     def ba_landmarks(self, cams=None):
         """(X (3, L), cam (K,), point (K,), uv (2, K), sigma (2, K)) when settings['ba_landmarks'] is true and the scene holds landmarks and
         observations, else None.  Validated on the host, before any GPU call: the flag is a bool, the arrays are finite with positive sigmas
         (inf = that axis unknown) and landmark indices inside [0, L), and the solver must be 'lm'.  ``cams``: the BA's camera set --
         observations of other cameras are left out and the camera id becomes the index in ``cams`` (None: ids as they are)."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        v = st.get('ba_landmarks', False)
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError("settings['ba_landmarks'] must be true or false, not %r" % (v,))
-        if not v:
+        if not _settings.needs_lm(_settings.as_dict(self.settings), 'ba_landmarks', 'landmarks'):
             return None
-        if st.get('ba_solver', 'trf') != 'lm':
-            raise ValueError("settings['ba_landmarks'] needs settings['ba_solver'] = 'lm' (the TRF + LSMR solver takes no landmarks), "
-                             "not %r" % (st.get('ba_solver', 'trf'),))
         X, ob = getattr(self, 'landmarks', None), getattr(self, 'landmark_observations', None)
         if X is None or ob is None:
             return None
@@ -671,20 +570,6 @@ class Scene:
             return None
         return X.copy(), cam.astype(np.int32), ob[1].astype(np.int32), ob[2:4].copy(), ob[4:6].copy()
 
-    @staticmethod
-    def _apply_landmarks(h, lm):
-        """The landmarks in force on the handle are ``lm`` (None: none), set only when they differ, as with the priors."""
-        if lm is None:
-            if h.num_landmark_observations:
-                h.set_landmarks(None, None, None, None, None)
-                h._landmarks = None
-            return
-        cur = getattr(h, '_landmarks', None)
-        if cur is not None and h.num_landmark_observations == lm[1].size and all(np.array_equal(a, b) for a, b in zip(cur, lm)):
-            return
-        h.set_landmarks(*lm)
-        h._landmarks = lm
-
     def triangulate_landmarks(self):
         """(ids, Y (3, len(ids))): every landmark seen by at least two cameras that have a pose, triangulated from the current cameras by a
         multi-view DLT on the host (undistorted, normalised image points; L is tens).  Whatever the settings say."""
@@ -692,8 +577,7 @@ class Scene:
         if X is None or ob is None:
             return np.empty(0, dtype=np.int64), np.empty((3, 0))
         X, ob = check_landmarks(X, ob, 'Scene.landmarks')
-        st = self.settings if isinstance(self.settings, dict) else {}
-        undist = bool(st.get('undist_points', False))
+        undist = bool(_settings.as_dict(self.settings).get('undist_points', False))
         ids, Y = [], []
         for l in range(X.shape[1]):
             rows, seen = [], set()
@@ -742,35 +626,13 @@ class Scene:
         """(t (K,), P (3, K), sigma (3, K)) when settings['ba_position_priors'] is true and ``self.position_priors`` holds priors, else
         None.  Validated on the host, before any GPU call: the flag is a bool, the array is (7, K) of finite t, x, y, z and positive
         sigmas (inf = that axis unknown), and the solver must be 'lm'."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        v = st.get('ba_position_priors', False)
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError("settings['ba_position_priors'] must be true or false, not %r" % (v,))
-        if not v:
+        if not _settings.needs_lm(_settings.as_dict(self.settings), 'ba_position_priors', 'position priors'):
             return None
-        if st.get('ba_solver', 'trf') != 'lm':
-            raise ValueError("settings['ba_position_priors'] needs settings['ba_solver'] = 'lm' (the TRF + LSMR solver takes no position priors), "
-                             "not %r" % (st.get('ba_solver', 'trf'),))
         pp = getattr(self, 'position_priors', None)
         if pp is None:
             return None
         pp = check_position_priors(pp, 'Scene.position_priors')
         return pp[0].copy(), pp[1:4].copy(), pp[4:7].copy()
-
-    @staticmethod
-    def _apply_position_priors(h, priors):
-        """The priors in force on the handle are ``priors`` (None: none), set only when they differ -- a handle that has them already keeps
-        what its last solve carried over, as with the loss and the mask."""
-        if priors is None:
-            if h.num_position_priors:
-                h.set_position_priors(None, None, None)
-                h._position_priors = None
-            return
-        cur = getattr(h, '_position_priors', None)
-        if cur is not None and h.num_position_priors == priors[0].size and all(np.array_equal(a, b) for a, b in zip(cur, priors)):
-            return
-        h.set_position_priors(*priors)
-        h._position_priors = priors
 
     def _active_position_priors(self):
         """(t, P) of the priors whose time lies in an interval of the spline (closed ends), whatever the settings say."""
@@ -835,50 +697,23 @@ class Scene:
 
     def ba_covariance_enabled(self):
         """settings['ba_covariance'] validated (a bool; absent = False): host only."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        v = st.get('ba_covariance', False)
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError("settings['ba_covariance'] must be true or false, not %r" % (v,))
-        return bool(v)
+        return _settings.flag(_settings.as_dict(self.settings), 'ba_covariance')
 
     def ba_kinematics_enabled(self):
         """settings['ba_kinematics'] validated (a bool; absent = False): host only."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        v = st.get('ba_kinematics', False)
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError("settings['ba_kinematics'] must be true or false, not %r" % (v,))
-        return bool(v)
+        return _settings.flag(_settings.as_dict(self.settings), 'ba_kinematics')
 
     def ba_detection_covariance_enabled(self):
         """settings['ba_detection_covariance'] validated (a bool; absent = False): host only."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        v = st.get('ba_detection_covariance', False)
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError("settings['ba_detection_covariance'] must be true or false, not %r" % (v,))
-        return bool(v)
+        return _settings.flag(_settings.as_dict(self.settings), 'ba_detection_covariance')
 
     def ba_register_enabled(self):
-        """settings['ba_register'] validated (a bool; absent = False): host only.  True makes the incremental loop register every new
-        camera against the held trajectory (``register_camera``) between ``get_camera_pose`` and ``triangulate``."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        v = st.get('ba_register', False)
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError("settings['ba_register'] must be true or false, not %r" % (v,))
-        return bool(v)
+        """settings['ba_register'] validated (a bool; absent = False): host only.  True: the incremental loop calls ``register_camera`` on every new camera."""
+        return _settings.flag(_settings.as_dict(self.settings), 'ba_register')
 
     def ba_register_beta_search(self):
-        """settings['ba_register_beta_search'] validated: absent / None -> None, else (half_width, step) in frames, two finite numbers with
-        half_width >= 0 and step > 0.  Host only."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        v = st.get('ba_register_beta_search', None)
-        if v is None:
-            return None
-        ok = isinstance(v, (list, tuple)) and len(v) == 2 and all(
-            not isinstance(q, (bool, np.bool_)) and isinstance(q, (int, float, np.integer, np.floating)) and np.isfinite(q) for q in v)
-        if not ok or not (v[0] >= 0 and v[1] > 0):
-            raise ValueError("settings['ba_register_beta_search'] must be [half_width, step] in frames (finite, half_width >= 0, step > 0), "
-                             "not %r" % (v,))
-        return float(v[0]), float(v[1])
+        """settings['ba_register_beta_search'] validated: absent / None -> None, else (half_width, step) in frames, finite, half_width >= 0, step > 0.  Host only."""
+        return _settings.register_beta_search(_settings.as_dict(self.settings))
 
     @staticmethod
     def register_rank(status, inliers, cost, ks):
@@ -901,7 +736,7 @@ class Scene:
         so, and the call prints it.  The camera's detections have not been through ``remove_outliers``: least squares under the linear
         loss gives way to gross outliers that PnP + RANSAC ignored (a robust ``ba_loss`` is the remedy, and then the winner is kept)."""
         cam_id = int(cam_id)
-        st = self.settings if isinstance(self.settings, dict) else {}
+        st = _settings.as_dict(self.settings)
         if self.ba_landmarks() is not None:          # (the setting is on AND the scene holds landmarks and clicks)
             from .. import ba as _ba
             raise _ba.UnsupportedBySolver("register_camera: settings['ba_landmarks'] is on -- the per-camera problem holds no landmark rows and "
@@ -919,19 +754,15 @@ class Scene:
             raise ValueError('register_camera: camera %d has no pose yet (get_camera_pose first)' % cam_id)
         if not getattr(self, 'spline', None) or not self.spline.get('tck'):
             raise ValueError('register_camera: the scene has no trajectory spline')
-        loss, f_scale = self.ba_loss()
+        loss = self.ba_loss()
         self.alpha, self.beta, self.rs = (np.asarray(v, dtype=np.float64) for v in (self.alpha, self.beta, self.rs))
         prob = self._ba_problem([cam_id], rs=rs, rs_bounds=rs_bounds)
         x = self._pack(prob, [cam_id])
-        P = prob.P
-        part = {'K': range(0, 4), 'R': range(4, 7), 't': range(7, 10), 'd': range(10, 15)} if calib else {'R': range(0, 3), 't': range(3, 6)}
-        mask = np.zeros(3 + P, dtype=bool)
-        for name in hold:
-            if name in ('alpha', 'beta', 'rs'):
-                mask[('alpha', 'beta', 'rs').index(name)] = True
-            elif name in part:                       # (K, d without opt_calib are not in x: held by construction)
-                mask[[3 + j for j in part[name]]] = True
-        start = x[:3 + P].copy()[None, :]
+        lay = _problem.HeadLayout(calib)
+        mask = np.zeros(lay.size, dtype=bool)
+        for name in hold:                            # (K, d without opt_calib are not in x: held by construction)
+            mask[lay.indices(0, name)] = True
+        start = x[:lay.size].copy()[None, :]
         if beta_search is not None:
             kmax = int(np.floor(beta_search[0] / beta_search[1] + 1e-9))
             ks = np.arange(-kmax, kmax + 1)
@@ -941,10 +772,7 @@ class Scene:
             ks = np.zeros(1, dtype=np.int64)
         thres = float(st.get('thres_outlier', 0) if thres is None else thres)
         with self._handle(prob) as h:
-            if (loss, f_scale) != h.loss:
-                h.set_loss(loss, f_scale)
-            if mask.any():
-                h.set_frozen(mask)
+            h.configure(loss=loss, frozen=mask)
             res = h.register_cameras(x, np.zeros(start.shape[0], dtype=np.int32), start=start, max_nfev=max_nfev, inlier_thres=thres)
             # the camera as it came in, scored the same way (one evaluation, nothing moves)
             came = h.register_cameras(x, [0], max_nfev=1, inlier_thres=thres) if (keep_start and thres > 0) else None
@@ -963,7 +791,7 @@ class Scene:
                   % (cam_id, res.start_inliers, thres, int(res.inliers[best])))
             return res
         xb = x.copy()
-        xb[:3 + P] = res.params[best]
+        xb[:lay.size] = res.params[best]
         alpha, beta, rs_new, cam_states, _ = _problem.unpack_x(prob, xb)
         self.alpha[cam_id], self.beta[cam_id], self.rs[cam_id] = alpha[0], beta[0], rs_new[0]
         for name in ('K', 'd') if calib else ():     # (a held part keeps the object it has: no round trip through x)
@@ -996,7 +824,7 @@ class Scene:
         tck, interval = self.spline['tck'], self.spline['int']
         ts = np.asarray(self.traj[0] if t is None else t, dtype=np.float64)
         fps = float(self.cameras[self.ref_cam].fps if fps is None else fps)
-        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
+        device = self._device()
         D, which = _spline.evaluate_der(tck, interval, ts, nder=2, device=device)
         dist, _, length = _spline.path_length(tck, interval, ts, device=device)
         before = np.concatenate(([0.0], np.cumsum(length)[:-1]))
@@ -1019,9 +847,7 @@ class Scene:
 
     def ba_param_names(self):
         """Names of the P parameters of one camera in x (Camera.P2vector order)."""
-        if self.settings['opt_calib']:
-            return ['fx', 'fy', 'cx', 'cy', 'r1', 'r2', 'r3', 't1', 't2', 't3', 'k1', 'k2', 'p1', 'p2', 'k3']
-        return ['r1', 'r2', 'r3', 't1', 't2', 't3']
+        return _problem.HeadLayout(self.settings['opt_calib']).names
 
     def ba_covariance(self, cams, t=None, sigma2=None, rs=False, motion_reg=False, motion_weights=1, rs_bounds=False):
         """Covariance of the BA estimate over the cameras ``cams`` at the scene's current state (``mvus_ba_covariance``): built on the
@@ -1045,35 +871,20 @@ class Scene:
         prob = self._ba_problem(cams, rs=rs, motion_reg=motion_reg, motion_weights=motion_weights, rs_bounds=rs_bounds)
         x = self._pack(prob, cams)
         self.ba_mode()                             # validates the ba_* settings
-        loss, f_scale = self.ba_loss()
-        h = self._resident_handle(prob, cams)
-        if h.loss != (loss, f_scale):
-            h.set_loss(loss, f_scale)
-        mask, cur = self.ba_frozen_mask(cams), h.frozen
-        if not np.array_equal(mask, cur if cur is not None else np.zeros(mask.size, dtype=bool)):
-            h.set_frozen(mask)
-        self._apply_position_priors(h, self.ba_position_priors())
-        self._apply_landmarks(h, self.ba_landmarks(cams))
-        return h, prob, x
+        return self._configured_handle(prob, cams), prob, x
 
     def _store_covariance(self, cv, cams, prob, t):
         """``self.covariance`` from the namespace of ``BAHandle.covariance`` / ``detection_covariance`` (the dict ``ba_covariance`` documents)."""
         from .. import spline as _spline
-        C, P = len(cams), prob.P
-        names = self.ba_param_names()
+        lay = _problem.HeadLayout(prob.opt_calib, len(cams))
         sd = np.sqrt(np.diag(cv.cam))
-        cam_std = {}
-        for k, cam in enumerate(cams):
-            d = {'alpha': float(sd[k]), 'beta': float(sd[C + k]), 'rs': float(sd[2 * C + k])}
-            d.update({name: float(sd[3 * C + k * P + j]) for j, name in enumerate(names)})
-            cam_std[int(cam)] = d
+        cam_std = {int(cam): {name: float(sd[lay.index(k, name)]) for name in list(lay.HEAD) + lay.names} for k, cam in enumerate(cams)}
         ts = np.asarray(self.traj[0] if t is None else t, dtype=np.float64)
-        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
-        pos_cov, _ = _spline.cov_evaluate(self.spline['tck'], self.spline['int'], cv.band, ts, device=device)
+        pos_cov, _ = _spline.cov_evaluate(self.spline['tck'], self.spline['int'], cv.band, ts, device=self._device())
         with np.errstate(invalid='ignore'):
             pos_std = np.sqrt(np.einsum('tii->ti', pos_cov))
-        self.covariance = {'cams': [int(c) for c in cams], 'param_names': names, 'sigma2': float(cv.sigma2), 'dof': int(cv.dof),
-                           'cam_cov': cv.cam, 'estimated_cam': cv.estimated[:C * (3 + P)].copy(), 'cam_std': cam_std, 'band': cv.band,
+        self.covariance = {'cams': [int(c) for c in cams], 'param_names': lay.names, 'sigma2': float(cv.sigma2), 'dof': int(cv.dof),
+                           'cam_cov': cv.cam, 'estimated_cam': cv.estimated[:lay.size].copy(), 'cam_std': cam_std, 'band': cv.band,
                            't': ts.copy(), 'pos_cov': pos_cov, 'pos_std': pos_std}
         return self.covariance
 
@@ -1116,39 +927,13 @@ class Scene:
         with np.errstate(invalid='ignore'):
             return {cam: np.asarray(d['t2']) > thr for cam, d in result['per_cam'].items()}
 
+    FREEZE_NAMES = _settings.FREEZE_NAMES
     FREEZE_NAMES = ('alpha', 'beta', 'rs', 'R', 't', 'K', 'd')
 
     def ba_freeze(self):
         """({camera index: names}, gauge) of settings['ba_freeze'] / settings['ba_gauge'], validated: host only, raises ValueError before
         any GPU call.  Without the keys: ({}, 'free') -- the reference's problem."""
-        st = self.settings if isinstance(self.settings, dict) else {}
-        gauge = st.get('ba_gauge', 'free')
-        if not isinstance(gauge, str) or gauge not in ('free', 'anchor'):
-            raise ValueError("settings['ba_gauge'] must be 'free' or 'anchor', not %r" % (gauge,))
-        raw = st.get('ba_freeze', {})
-        if raw is None:
-            raw = {}
-        if not isinstance(raw, dict):
-            raise ValueError("settings['ba_freeze'] must map camera indices to lists of names from %s, not %r" % (list(self.FREEZE_NAMES), raw))
-        freeze = {}
-        for key, names in raw.items():
-            try:                                 # (a config.json has string keys)
-                cam = int(key)
-                if isinstance(key, (bool, float)) or str(cam) != str(key).strip():
-                    raise ValueError
-            except (TypeError, ValueError):
-                raise ValueError("settings['ba_freeze']: %r is not a camera index" % (key,)) from None
-            if cam < 0:
-                raise ValueError("settings['ba_freeze']: %r is not a camera index" % (key,))
-            if isinstance(names, str) or not isinstance(names, (list, tuple, set, frozenset)):
-                raise ValueError("settings['ba_freeze'][%r] must be a list of names from %s, not %r" % (key, list(self.FREEZE_NAMES), names))
-            for name in names:
-                if not isinstance(name, str) or name not in self.FREEZE_NAMES:
-                    raise ValueError("settings['ba_freeze'][%r]: unknown name %r (one of %s)" % (key, name, list(self.FREEZE_NAMES)))
-                if name in ('K', 'd') and not st.get('opt_calib', False):
-                    raise ValueError("settings['ba_freeze'][%r]: %r is a parameter only with settings['opt_calib'] (fixed calibration is not in x)" % (key, name))
-            freeze.setdefault(cam, set()).update(names)
-        return freeze, gauge
+        return _settings.freeze(_settings.as_dict(self.settings))
 
     def ba_frozen_mask(self, cams):
         """bool[C * (3 + P)] over the camera-side head of x (pack_x order: alpha(C), beta(C), rs(C), P parameters per camera) for a BA over
@@ -1157,49 +942,28 @@ class Scene:
         scene about the first camera's centre C_0 (t_1 = -R_1 C_1, C_1 -> C_0 + s (C_1 - C_0)): with the first pose held the similarity has
         only that scaling left, and holding a component it moves removes it.  Pure host function; no GPU call."""
         freeze, gauge = self.ba_freeze()
-        st = self.settings if isinstance(self.settings, dict) else {}
         cams = list(cams)
         C = len(cams)
-        calib = bool(st.get('opt_calib', False))
-        P = 15 if calib else 6                    # fx fy cx cy | rvec | t | k1 k2 p1 p2 k3  or  rvec | t  (Camera.P2vector)
-        part = {'K': range(0, 4), 'R': range(4, 7), 't': range(7, 10), 'd': range(10, 15)} if calib else {'R': range(0, 3), 't': range(3, 6)}
-        mask = np.zeros(C * (3 + P), dtype=bool)
+        lay = _problem.HeadLayout(bool(_settings.as_dict(self.settings).get('opt_calib', False)), C)
+        mask = np.zeros(lay.size, dtype=bool)
         for k, cam in enumerate(cams):
             for name in freeze.get(int(cam), ()):
-                if name in ('alpha', 'beta', 'rs'):
-                    mask[('alpha', 'beta', 'rs').index(name) * C + k] = True
-                else:
-                    mask[[3 * C + k * P + j for j in part[name]]] = True
+                mask[lay.indices(k, name)] = True
         if gauge == 'anchor' and C >= 1:
-            mask[[3 * C + j for j in list(part['R']) + list(part['t'])]] = True
+            mask[lay.indices(0, 'R') + lay.indices(0, 't')] = True
             if C >= 2:
                 c0, c1 = self.cameras[cams[0]], self.cameras[cams[1]]
                 R0, R1 = np.asarray(c0.R, dtype=np.float64), np.asarray(c1.R, dtype=np.float64)
                 centre0 = -R0.T @ np.ravel(np.asarray(c0.t, dtype=np.float64))
                 centre1 = -R1.T @ np.ravel(np.asarray(c1.t, dtype=np.float64))
                 comp = int(np.argmax(np.abs(R1 @ (centre0 - centre1))))
-                mask[3 * C + P + part['t'][comp]] = True
+                mask[lay.indices(1, 't')[comp]] = True
         return mask
 
     def ba_loss(self):
-        """(MVUS_LOSS_* code, f_scale) of settings['ba_loss'] / settings['ba_f_scale']: the ``loss`` and ``f_scale`` arguments of
-        scipy's least_squares, which the reference never passes ('linear', 1.0 -- also the defaults here).  A loss other than
-        'linear' needs ``ba_solver: 'lm'`` with the analytic Jacobian."""
-        from .. import ba as _ba
-        st = self.settings if isinstance(self.settings, dict) else {}
-        name = st.get('ba_loss', 'linear')
-        if not isinstance(name, str) or name not in _ba.LOSS_NAMES:
-            raise ValueError("settings['ba_loss'] must be one of %s, not %r" % (sorted(_ba.LOSS_NAMES), name))
-        f_scale = st.get('ba_f_scale', 1.0)
-        if isinstance(f_scale, bool) or not isinstance(f_scale, (int, float, np.integer, np.floating)) or not np.isfinite(f_scale) or not f_scale > 0:
-            raise ValueError("settings['ba_f_scale'] must be a finite positive number, not %r" % (f_scale,))
-        if name != 'linear':
-            if st.get('ba_solver', 'trf') != 'lm':
-                raise ValueError("settings['ba_loss'] = %r needs settings['ba_solver'] = 'lm' (the TRF + LSMR solver has no robust loss), not %r"
-                                 % (name, st.get('ba_solver', 'trf')))
-            if st.get('ba_jacobian', 'analytic') != 'analytic':
-                raise ValueError("settings['ba_loss'] = %r needs settings['ba_jacobian'] = 'analytic', not %r" % (name, st.get('ba_jacobian')))
-        return _ba.LOSS_NAMES[name], float(f_scale)
+        """(MVUS_LOSS_* code, f_scale) of settings['ba_loss'] / settings['ba_f_scale']: the ``loss`` and ``f_scale`` arguments of scipy's least_squares, which
+        the reference never passes ('linear', 1.0 -- also the defaults here).  A loss other than 'linear' needs ``ba_solver: 'lm'`` with the analytic Jacobian."""
+        return _settings.loss(_settings.as_dict(self.settings))
 
     def remove_outliers(self, cams, thres=30, verbose=False):
         """Drop detections whose reprojection error is >= thres (common.py:700-717); the mask is computed by
@@ -1207,8 +971,7 @@ class Scene:
         if not thres:
             return
         cams = list(cams)
-        for i in cams:
-            self.detection_to_global(i)
+        self.detection_to_global(cams)
         # in place on the GPU only if the resident handle is over exactly these cameras AND still describes the current
         # scene (detections, knots, intervals, fixed K/d, undist_points): the reference always evaluates current state
         h = self._resident_for(cams) if self._ba_key == tuple(cams) else None
@@ -1243,7 +1006,7 @@ class Scene:
         new_cam = self.cameras[cam_id]
         assert new_cam.P is not None, 'The camera pose must be computed first'
         covered = self.spline['int']
-        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
+        device = self._device()
         self.detection_to_global(cam_id)
         mine = self.detections_global[cam_id]
         mine = mine[:, ~np.asarray(util.sampling(mine, covered)[1], dtype=bool)]      # only what the spline does not cover yet
@@ -1302,7 +1065,7 @@ class Scene:
         from .. import spline as _spline
         from .pnp import solve_pnp_ransac
         tck, interval = self.spline['tck'], self.spline['int']
-        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
+        device = self._device()
         self.detection_to_global(cam_id)
         det = self.detections_global[cam_id]
         _, idx = util.sampling(det, interval, belong=True)
@@ -1368,7 +1131,7 @@ class Scene:
         if len(self.cameras) < 2 or self.numCam < 2:
             raise NotImplementedError('init_traj: two-view initialisation needs at least two cameras with detections (this scene has '
                                       '%d); single-view reconstruction is not implemented' % min(len(self.cameras), self.numCam))
-        device = int(self.settings.get('device', 0)) if isinstance(self.settings, dict) else 0
+        device = self._device()
         self.select_most_overlap(init=True)
         t1, t2 = self.sequence[0], self.sequence[1]
         K1, K2 = self.cameras[t1].K, self.cameras[t2].K
@@ -1408,8 +1171,7 @@ class Scene:
         if not motion_reg:
             raise ValueError('error_motion: motion_reg=True is the only live mode (the reference returns an unbound name otherwise)')
         cams = [int(cams)] if isinstance(cams, (int, np.integer)) else list(cams)
-        for i in cams:
-            self.detection_to_global(i)
+        self.detection_to_global(cams)
         self.spline_to_traj()
         prob = self._ba_problem(cams[:1], motion_reg=True, motion_weights=motion_weights)
         with self._handle(prob) as tmp:
@@ -1417,122 +1179,6 @@ class Scene:
         out = f[2 * prob.M:]
         assert out.size == self.traj.shape[1], 'motion rows and trajectory samples do not correspond'
         return out
-
-
-def umeyama_similarity(X, Y):
-    """(s, R, T) minimising sum |s R X_i + T - Y_i|^2 over similarities (Umeyama 1991), X and Y (3, k) with k >= 3: R a proper rotation."""
-    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
-    mx, my = X.mean(axis=1, keepdims=True), Y.mean(axis=1, keepdims=True)
-    a, b = X - mx, Y - my
-    U, D, Vt = np.linalg.svd(b @ a.T / X.shape[1])
-    S = np.ones(3)
-    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
-        S[2] = -1.0
-    R = U @ np.diag(S) @ Vt
-    s = float(np.sum(D * S) / (np.sum(a * a) / X.shape[1]))
-    T = (my - s * (R @ mx)).ravel()
-    return s, R, T
-
-
-def _undistort_normalised(x0, y0, d):
-    """cv2.undistortPoints on normalised coordinates (five fixed-point iterations), host side"""
-    k1, k2, p1, p2, k3 = (list(d) + [0.0] * 5)[:5]
-    x, y = x0, y0
-    for _ in range(5):
-        r2 = x * x + y * y
-        ic = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
-        if ic < 0:
-            return x0, y0
-        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
-        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
-        x, y = (x0 - dx) * ic, (y0 - dy) * ic
-    return x, y
-
-
-def check_landmarks(X, ob, what='landmarks'):
-    """((3, L) landmarks, (6, K) observations: camera id, landmark, u, v, sigma_u, sigma_v), validated: finite positions and pixels, whole
-    non-negative camera ids, landmark indices inside [0, L), sigmas positive (inf allowed)."""
-    X, ob = np.asarray(X, dtype=np.float64), np.asarray(ob, dtype=np.float64)
-    if X.ndim != 2 or X.shape[0] != 3:
-        raise ValueError('%s must be a (3, L) array, not shape %s' % (what, X.shape))
-    if ob.ndim != 2 or ob.shape[0] != 6:
-        raise ValueError('%s: the observations must be a (6, K) array of camera, landmark, u, v, sigma_u, sigma_v, not shape %s' % (what, ob.shape))
-    if not np.all(np.isfinite(X)) or not np.all(np.isfinite(ob[:4])):
-        raise ValueError('%s: a position, an index or a pixel is not finite' % what)
-    if np.any(ob[:2] != np.floor(ob[:2])) or np.any(ob[0] < 0) or np.any(ob[1] < 0) or np.any(ob[1] >= X.shape[1]):
-        raise ValueError('%s: camera ids must be whole and >= 0, landmark indices whole and inside [0, %d)' % (what, X.shape[1]))
-    if np.any(np.isnan(ob[4:])) or np.any(ob[4:] <= 0):
-        raise ValueError('%s: sigma must be positive (inf leaves an axis out)' % what)
-    return X, ob
-
-
-def load_landmarks(path_points, path_observations, default_sigma=None):
-    """Two text files (``#`` comments): ``id x y z`` per landmark and ``camera id u v [sigma_u sigma_v]`` per click -> ((3, L), (6, K)) with the
-    ids replaced by the landmark's position in the first file.  Clicks without sigma columns take ``default_sigma`` (a positive number, or
-    two of them)."""
-    try:
-        a = np.loadtxt(path_points, dtype=np.float64, ndmin=2)
-        b = np.loadtxt(path_observations, dtype=np.float64, ndmin=2)
-    except ValueError as e:
-        raise ValueError('landmarks %s / %s: %s' % (path_points, path_observations, e)) from None
-    if a.shape[0] and a.shape[1] != 4:
-        raise ValueError('landmarks %s: %d columns, expected id x y z' % (path_points, a.shape[1]))
-    a = a.reshape(-1, 4)
-    ids = a[:, 0]
-    if np.any(ids != np.floor(ids)) or np.unique(ids).size != ids.size:
-        raise ValueError('landmarks %s: ids must be whole numbers, each once' % path_points)
-    if b.shape[0] == 0:
-        return a[:, 1:4].T.copy(), np.empty((6, 0))
-    if b.shape[1] == 4:
-        if default_sigma is None:
-            raise ValueError("landmark observations %s: columns camera id u v only -- give sigma_u sigma_v columns or 'landmark_sigma'" % path_observations)
-        sg = np.asarray(default_sigma, dtype=np.float64)
-        if sg.shape not in ((), (2,)) or isinstance(default_sigma, bool):
-            raise ValueError("'landmark_sigma' must be a positive number or two of them, not %r" % (default_sigma,))
-        b = np.hstack((b, np.broadcast_to(sg, (b.shape[0], 2))))
-    elif b.shape[1] != 6:
-        raise ValueError('landmark observations %s: %d columns, expected camera id u v [sigma_u sigma_v]' % (path_observations, b.shape[1]))
-    where = {int(i): k for k, i in enumerate(ids)}
-    unknown = [int(i) for i in b[:, 1] if i != np.floor(i) or int(i) not in where]
-    if unknown:
-        raise ValueError('landmark observations %s: ids %s are not in %s' % (path_observations, sorted(set(unknown)), path_points))
-    ob = b.T.copy()
-    ob[1] = [where[int(i)] for i in b[:, 1]]
-    X, ob = check_landmarks(a[:, 1:4].T.copy(), ob, 'landmarks %s' % path_points)
-    return X, ob
-
-
-def check_position_priors(pp, what='position priors'):
-    """A (7, K) float array of t, x, y, z, sigma_x, sigma_y, sigma_z, validated: finite t and positions, sigmas positive (inf allowed)."""
-    pp = np.asarray(pp, dtype=np.float64)
-    if pp.ndim != 2 or pp.shape[0] != 7:
-        raise ValueError('%s must be a (7, K) array of t, x, y, z, sigma_x, sigma_y, sigma_z, not shape %s' % (what, pp.shape))
-    if not np.all(np.isfinite(pp[:4])):
-        raise ValueError('%s: a time or a position is not finite' % what)
-    if np.any(np.isnan(pp[4:])) or np.any(pp[4:] <= 0):
-        raise ValueError('%s: sigma must be positive (inf leaves an axis out)' % what)
-    return pp
-
-
-def load_position_priors(path, default_sigma=None):
-    """A text file with the columns t x y z [sigma_x sigma_y sigma_z] (one prior per line, ``#`` comments) -> (7, K).  Files without the sigma
-    columns take ``default_sigma`` (a positive number, or three of them)."""
-    try:
-        a = np.loadtxt(path, dtype=np.float64, ndmin=2)
-    except ValueError as e:
-        raise ValueError('position priors %s: %s' % (path, e)) from None
-    if a.shape[0] == 0:
-        return np.empty((7, 0))
-    if a.shape[1] == 4:
-        if default_sigma is None:
-            raise ValueError("position priors %s: columns t x y z only -- give sigma_x sigma_y sigma_z columns or 'position_prior_sigma'" % path)
-        sg = np.asarray(default_sigma, dtype=np.float64)
-        if sg.shape not in ((), (3,)) or isinstance(default_sigma, bool):
-            raise ValueError("'position_prior_sigma' must be a positive number or three of them, not %r" % (default_sigma,))
-        a = np.hstack((a, np.broadcast_to(sg, (a.shape[0], 3))))
-    elif a.shape[1] != 7:
-        raise ValueError('position priors %s: %d columns, expected t x y z [sigma_x sigma_y sigma_z]' % (path, a.shape[1]))
-    return check_position_priors(a.T.copy(), 'position priors %s' % path)
 
 
 def create_scene(path_input):

@@ -240,3 +240,30 @@ def test_pipeline_from_files_on_disk(tmp_path):
     np.testing.assert_array_equal(back.spline['tck'][0][1][0], flight.spline['tck'][0][1][0])
     np.testing.assert_array_equal(back.cameras[1].P, flight.cameras[1].P)
     assert back._ba_handle is None
+
+
+def test_configured_handle_puts_the_scenes_own_landmarks_back():
+    """The resident handle carries what the Scene holds, not what it last happened to be told: (1) after Scene.BA its landmark rows are those
+    of a new handle given Scene.ba_landmarks directly, bit for bit; (2) after a direct set_landmarks with other clicks of the same count,
+    the configured resident handle has the Scene's rows again; (3) asked once more, nothing is sent."""
+    from test_landmarks_host import _scene_with_marks
+    from mvus_amd import ba
+    s, _, _, cams = _scene_with_marks('c1_pinhole_2cam', ba_solver='lm', ba_landmarks=True)
+    s.BA(2, max_iter=2)
+    h = s._ba_handle
+    prob = s._ba_problem(cams)
+    x = s._pack(prob, cams)
+    marks = s.ba_landmarks(cams)
+    with ba.BAHandle(prob) as fresh:
+        fresh.set_landmarks(*marks)
+        cost0, rows0 = fresh.landmark_cost(x, rows=True)
+    cost, rows = h.landmark_cost(x, rows=True)
+    assert cost == cost0 and np.array_equal(rows, rows0)                             # (1)
+    h.set_landmarks(*(marks[:3] + (marks[3] + 5.0,) + marks[4:]))
+    assert h.landmark_cost(x) != cost0 and np.array_equal(h.landmarks[3], marks[3] + 5.0)
+    assert s._configured_handle(prob, cams) is h                                     # (2)
+    cost, rows = h.landmark_cost(x, rows=True)
+    assert cost == cost0 and np.array_equal(rows, rows0)
+    assert len(h.landmarks) == len(marks) and all(np.array_equal(a, b) for a, b in zip(h.landmarks, marks))
+    held = h.landmarks
+    assert s._configured_handle(prob, cams) is h and h.landmarks is held             # (3)
